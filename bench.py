@@ -8,6 +8,7 @@ process per GPU.
                                                       # tools/dist_train.sh:8-9 of the reference
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
+    python bench.py --steps K --dump-outputs DIR     # + the last timed step's outputs as DIR/<name>.npy (rank 0)
 
 A "step" is one full forward of the detector (FSF.simple_test: voxelize -> DynamicScatterVFE -> SimpleSparseUNet ->
 neck -> projection + mask gather + image fusion + seg head -> camera-query grouping + SIR -> LiDAR-query pre-voxelize,
@@ -85,7 +86,16 @@ def parse():
     ap.add_argument("--no-train-block", action="store_true", help="skip the short training-step side measurement of the default run")
     ap.add_argument("--hot-path-only", action="store_true",
                     help="time stages 1-3 only (segmentor + fusion, camera queries, LiDAR queries), no heads / refine / NMS")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the timed path returned in its last step as DIR/<name>.npy (float64 for "
+                         "float64 and integer arrays, float32 otherwise; at most 64 MB in all, larger outputs as a fixed seeded sample of "
+                         "rows): the inputs depend on the arguments only, so two builds compare output for output")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.warmup < 0:
+        ap.error("--warmup must not be negative")
+    return args
 
 
 def build_model(device, dataset="nuscenes"):
@@ -988,6 +998,89 @@ def cpu_baseline(model_cpu, sweeps):
                        f"over-states the CPU rate of the full forward")
 
 
+# ---------------------------------------------------------------------------------------------------- output dump
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def _output_leaves(obj, name, acc, skipped):
+    """(name, array) for every array in the structure the timed path returned: dicts / lists / tuples by key and index, box containers
+    by their `.tensor`, deferred concatenations materialised, Python scalars as 0-d arrays."""
+    if isinstance(obj, (torch.Tensor, np.ndarray)):
+        acc.append((name, obj))
+    elif isinstance(obj, dict):
+        for k, v in obj.items():
+            _output_leaves(v, f"{name}.{k}" if name else str(k), acc, skipped)
+    elif isinstance(obj, (list, tuple)):
+        for i, v in enumerate(obj):
+            _output_leaves(v, f"{name}.{i}" if name else str(i), acc, skipped)
+    elif isinstance(getattr(obj, "tensor", None), torch.Tensor):
+        acc.append((name, obj.tensor))
+    elif callable(getattr(obj, "materialize", None)):
+        acc.append((name, obj.materialize()))
+    elif isinstance(obj, (bool, int, float)):
+        acc.append((name, np.asarray(obj)))
+    elif obj is not None:
+        skipped.append(name)
+
+
+def collect_outputs(out):
+    """Host copies of what one step returned: float64 stays float64, integer and bool arrays become float64 (exact), everything else
+    float32.  Called right after the timed region, before any later pass reuses the device buffers."""
+    leaves, skipped = [], []
+    _output_leaves(out, "", leaves, skipped)
+    arrays, names = [], set()
+    for name, a in leaves:
+        a = a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
+        a = a.astype(np.float64 if a.dtype == np.float64 or a.dtype.kind in "biu" else np.float32)
+        base = re.sub(r"[^A-Za-z0-9_.-]", "_", name) or "output"
+        name, j = base, 1
+        while name in names:
+            name, j = f"{base}_{j}", j + 1
+        names.add(name)
+        arrays.append((name, a))
+    return arrays, skipped
+
+
+def dump_outputs(arrays, skipped, directory, budget=DUMP_BUDGET_BYTES):
+    """Writes `directory`/<name>.npy.  When the arrays hold more than `budget` bytes, the largest are cut to a common size cap (what
+    fits under the budget with every smaller array whole): each keeps a sample of its rows (leading axes of length 1 dropped), drawn by a
+    generator seeded from the array's name and sorted, so that the same shape always keeps the same rows."""
+    import zlib
+
+    def rows_of(a):
+        while a.ndim > 1 and a.shape[0] == 1:
+            a = a[0]
+        return a
+
+    created = not os.path.isdir(directory)
+    os.makedirs(directory, exist_ok=True)
+    if created:  # (a directory this run made holds generated files only: keep it out of version control wherever it lies)
+        with open(os.path.join(directory, ".gitignore"), "w") as f:
+            f.write("*\n")
+    cap = None
+    if sum(a.nbytes for _, a in arrays) > budget:
+        cuttable = sorted(a.nbytes for _, a in arrays if rows_of(a).ndim > 0 and rows_of(a).shape[0] > 1)
+        left = budget - (1 << 20) - sum(a.nbytes for _, a in arrays if rows_of(a).ndim == 0 or rows_of(a).shape[0] <= 1)  # (1 MB: headers)
+        for i, nb in enumerate(cuttable):
+            if nb * (len(cuttable) - i) > left:
+                cap = max(0, left) // (len(cuttable) - i)
+                break
+            left -= nb
+    sampled, written = {}, 0
+    for name, a in arrays:
+        if cap is not None and a.nbytes > cap and rows_of(a).ndim > 0 and rows_of(a).shape[0] > 1:
+            a = rows_of(a)
+            k = max(1, cap // (a.nbytes // a.shape[0]))
+            seed = zlib.crc32(name.encode())
+            rows = np.sort(np.random.default_rng(seed).choice(a.shape[0], size=k, replace=False))
+            sampled[name] = dict(rows=int(k), of=int(a.shape[0]), seed=seed)
+            a = a[rows]
+        np.save(os.path.join(directory, name + ".npy"), a)
+        written += a.nbytes
+    return dict(dir=os.path.abspath(directory), arrays=len(arrays), bytes=written, budget_bytes=budget, sampled=sampled,
+                **({"not_arrays": skipped} if skipped else {}))
+
+
 # ------------------------------------------------------------------------------------------------------ launching
 def _free_port():
     s = socket.socket()
@@ -1077,6 +1170,8 @@ def main():
         g = [torch.zeros(1, dtype=torch.float64, device=device) for _ in range(world)]
         dist.all_gather(g, torch.tensor([per_rank[0]], dtype=torch.float64, device=device))
         per_rank = [float(x.item()) for x in g]
+    # (host copies of the last timed step's outputs, taken before any later pass can reuse the buffers they live in)
+    dumped = collect_outputs(out) if args.dump_outputs and rank == 0 else None
 
     result = None
     last = pool[(args.warmup + args.steps - 1) % nframes]
@@ -1131,6 +1226,8 @@ def main():
         }
         if args.trained_like:
             result["metric"] += " (trained-like variant: calibrated foreground / candidate counts, 40 masks per frame)"
+        if dumped is not None:
+            result["dump_outputs"] = dump_outputs(*dumped, args.dump_outputs)
     ms_plain = None
     if not args.train:  # (all ranks, outside the timed region) the same loop WITHOUT announcing the next frame: rounds 1-5's loop
         ms_plain = result["ms_per_step"] if rank == 0 else None

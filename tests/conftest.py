@@ -84,6 +84,33 @@ def build_av2_fsf(perturb_image_branch=False):
     return model
 
 
+def config_digest(obj):
+    """sha256 of a config value (dicts, lists, tuples, scalars) in a canonical JSON form: key order ignored, tuples kept apart from
+    lists, ints and floats compared by value — equal digests mean `==` config values.  tests/golden/reference_configs.json holds these
+    digests of the reference's own configs, so that the drop-in tests compare against them without the reference tree."""
+    import hashlib
+    import json
+
+    def canon(o):
+        if isinstance(o, dict):
+            return {str(k): canon(v) for k, v in o.items()}
+        if isinstance(o, tuple):
+            return {"__tuple__": [canon(v) for v in o]}
+        if isinstance(o, list):
+            return [canon(v) for v in o]
+        if isinstance(o, (int, float)) and not isinstance(o, bool):
+            return float(o)
+        return o
+
+    return hashlib.sha256(json.dumps(canon(obj), sort_keys=True).encode()).hexdigest()
+
+
+def state_shapes_digest(model):
+    """(number of entries, sha256 of the sorted {name: shape} map) of a model's state_dict."""
+    shapes = sorted((k, list(v.shape)) for k, v in model.state_dict().items())
+    return len(shapes), config_digest(shapes)
+
+
 def param_checksum(model):
     """float64 sum of |p| over parameters and buffers: detects a model that differs from the one a golden was made with."""
     import torch

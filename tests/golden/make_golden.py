@@ -6,7 +6,7 @@ Runs only in the build container (needs /root/reference).  Nothing of the refere
 un-installable dependencies, and pure-torch methods of `FSF` / `Voxel2PointScatterNeck` / `SIR` are lifted
 from their files with `ast` and executed.  Only inputs + outputs are saved (.npz).
 
-    python tests/golden/make_golden.py            # rewrites tests/golden/*.npz
+    python tests/golden/make_golden.py            # rewrites tests/golden/*.npz and reference_configs.json
 
 Fixtures are DATA (seeded inputs, expected outputs); the GPU box never sees /root/reference.
 """
@@ -569,6 +569,49 @@ def gen_input_pipeline(rng):
         padded=padded.numpy(), saved=saved.numpy(), normed=normed.numpy(), single_anno=single.numpy())
 
 
+def gen_reference_configs():
+    """The reference's two configs (projects/configs/nuScenes/FSF_nuScenes_config.py, Argoverse2/FSF_AV2_config.py) loaded through
+    compat.Config and built through the plugin registries; stored are facts about them, not their contents: every `type=` name,
+    digests of the model sections (tests/conftest.py::config_digest), the state_dict shape digest of the model built with the
+    reference's own kwargs, its parameter count.  tests/test_config_surface.py checks the repository's configs against these."""
+    import json
+
+    root = os.path.dirname(os.path.dirname(OUT))
+    sys.path.insert(0, root)
+    sys.path.insert(0, os.path.join(root, "tests"))
+    from conftest import config_digest, state_shapes_digest
+    from fullysparsefusion_amd import mmdet3d_plugin as plugin
+    from fullysparsefusion_amd.compat import Config
+
+    def types_of(o, acc):
+        if isinstance(o, dict):
+            if isinstance(o.get("type"), str):
+                acc.add(o["type"])
+            for v in o.values():
+                types_of(v, acc)
+        elif isinstance(o, (list, tuple)):
+            for v in o:
+                types_of(v, acc)
+        return acc
+
+    def facts(rel):
+        cfg = Config.fromfile(os.path.join(REF, "projects/configs", rel))
+        model = plugin.build_model(cfg.model, train_cfg=cfg.get("train_cfg"), test_cfg=cfg.get("test_cfg"))
+        n, digest = state_shapes_digest(model)
+        heads = {h: {k: config_digest(v) for k, v in cfg.model[h].items()} for h in ("bbox_head", "frustum_obj_head")}
+        return dict(plugin=cfg.plugin, plugin_dir=cfg.plugin_dir, types=sorted(types_of(cfg.to_dict(), set())),
+                    model={k: config_digest(v) for k, v in cfg.model.items()}, heads=heads,
+                    refined_obj_head_0_test_cfg=config_digest(cfg.model.refined_obj_head[0].test_cfg),
+                    frustum_obj_head_test_cfg=config_digest(cfg.model.frustum_obj_head.test_cfg),
+                    state_dict_entries=n, state_dict_shapes=digest, num_extra_stages=model.num_extra_stages,
+                    parameters=sum(p.numel() for p in model.parameters()))
+
+    out = dict(nuscenes=facts("nuScenes/FSF_nuScenes_config.py"), av2=facts("Argoverse2/FSF_AV2_config.py"))
+    with open(os.path.join(OUT, "reference_configs.json"), "w") as f:
+        json.dump(out, f, indent=1, sort_keys=True)
+        f.write("\n")
+
+
 def main():
     assert os.path.isdir(REF), "the reference tree is only available in the build container"
     install_stubs()
@@ -588,6 +631,7 @@ def main():
     gen_sir_flow(sst, rng)
     gen_refine_glue(np.random.default_rng(777))
     gen_input_pipeline(np.random.default_rng(4242))
+    gen_reference_configs()
     for f in sorted(os.listdir(OUT)):
         if f.endswith(".npz"):
             print(f, os.path.getsize(os.path.join(OUT, f)) // 1024, "KiB")

@@ -30,3 +30,24 @@ def test_bench_default_line_has_roofline_and_hbm_table():
     assert "hbm" not in roof and "frac_of_fp32_pipe_peak" not in json.dumps(roof)
     for k in ("linear_norm_act", "seg_reduce", "sir_input"):
         assert 0 < roof["hbm_in_situ"][k]["frac_of_hbm_peak"] < 1
+
+
+@pytest.mark.gpu
+def test_bench_dump_outputs_holds_the_last_timed_steps_results(tmp_path):
+    """`--dump-outputs DIR`: the results the timed path returned in its last step (FSF.simple_test: boxes, scores, labels of the frame)
+    as DIR/<name>.npy, and `--steps` sets the number of timed steps."""
+    import numpy as np
+
+    dump = tmp_path / "dump"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--no-roofline",
+                        "--no-trained-like", "--no-h2d", "--no-train-block", "--dump-outputs", str(dump)],
+                       capture_output=True, text=True, timeout=900, cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-3000:]
+    d = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+    assert d["steps"] == 3 and d["ms_per_step"] > 0
+    files = sorted(f for f in os.listdir(dump) if f.endswith(".npy"))
+    assert files == ["0.boxes_3d.npy", "0.labels_3d.npy", "0.scores_3d.npy"] and d["dump_outputs"]["arrays"] == 3
+    boxes, scores, labels = (np.load(dump / f) for f in ("0.boxes_3d.npy", "0.scores_3d.npy", "0.labels_3d.npy"))
+    assert boxes.dtype == scores.dtype == np.float32 and labels.dtype == np.float64
+    assert boxes.shape == (d["config"]["boxes_out"], 9) and scores.shape == labels.shape == (boxes.shape[0],) and boxes.shape[0] > 0
+    assert np.isfinite(boxes).all() and (labels == np.round(labels)).all()

@@ -1,15 +1,19 @@
 """CPU: the drop-in boundary b1: mmcv-style configs load through compat.Config, every `type=`
 resolves against the plugin registries, and the model builds with the reference's own kwargs."""
+import json
 import os
 
 import pytest
+from conftest import GOLDEN, config_digest, state_shapes_digest
 
 from fullysparsefusion_amd import mmdet3d_plugin as plugin
 from fullysparsefusion_amd.compat import Config
 from fullysparsefusion_amd.mmdet3d_plugin import registry as R
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF_CFG = "/root/reference/projects/configs/nuScenes/FSF_nuScenes_config.py"
+# the reference's own configs, recorded as facts (type names, section digests, parameter shapes): tests/golden/make_golden.py
+with open(os.path.join(GOLDEN, "reference_configs.json")) as _f:
+    REF_FACTS = json.load(_f)
 # types owned by mmcv's runner / torch.optim / the conv_cfg-act_cfg mini-dialect, not by plugin registries
 EXTERNAL = {"AdamW", "Conv1d", "ReLU", "EpochBasedRunner", "TensorboardLoggerHook", "TextLoggerHook", "cyclic", "CosineAnnealing"}
 REGS = [R.MODELS, R.SEGMENTORS, R.VOXEL_ENCODERS, R.MIDDLE_ENCODERS, R.BBOX_CODERS, R.BBOX_ASSIGNERS, R.PIPELINES, R.DATASETS,
@@ -32,6 +36,10 @@ def unresolved(cfg_dict):
 
     walk(cfg_dict)
     return missing
+
+
+def unresolved_types(names):
+    return {t for t in names if t not in EXTERNAL and not any(t in r for r in REGS)}
 
 
 def test_own_config_builds():
@@ -70,50 +78,45 @@ def test_config_merge_semantics(tmp_path):
     assert cfg.a.y.w == 9 and cfg.d == 4
 
 
-@pytest.mark.skipif(not os.path.exists(REF_CFG), reason="reference tree only exists in the build container")
 def test_reference_config_loads_and_builds_unchanged():
-    cfg = Config.fromfile(REF_CFG)
-    assert cfg.plugin is True and cfg.plugin_dir == "projects/mmdet3d_plugin/"
-    assert not unresolved(cfg.to_dict()), unresolved(cfg.to_dict())
-    model = plugin.build_model(cfg.model, train_cfg=cfg.get("train_cfg"), test_cfg=cfg.get("test_cfg"))
+    """The reference's FSF_nuScenes_config.py, as recorded by tests/golden/make_golden.py::gen_reference_configs (loaded through
+    compat.Config, built with its own train_cfg / test_cfg): every `type=` it names resolves, and the repository's own config
+    describes the same model, section for section and parameter shape for parameter shape."""
+    ref = REF_FACTS["nuscenes"]
+    assert ref["plugin"] is True and ref["plugin_dir"] == "projects/mmdet3d_plugin/"
+    assert not unresolved_types(ref["types"]), unresolved_types(ref["types"])
     own = Config.fromfile(os.path.join(ROOT, "configs", "fsf_nuscenes.py"))
     for key in ["segmentor", "backbone", "frustum_sir", "cluster_assigner", "test_cfg", "mlp_cfg", "bbox_coder", "roi_extractor",
                 "single_refine_sir_layer", "refine_encode_2d_mlp_cfg"]:
-        assert cfg.model[key] == own.model[key], key
+        assert config_digest(own.model[key]) == ref["model"][key], key
     for head in ["bbox_head", "frustum_obj_head"]:  # inference-relevant head arguments (assigners / losses are train-time)
         for key in ["type", "num_classes", "bbox_coder", "in_channel", "shared_mlp_dims", "tasks", "class_names", "common_attrs",
                     "num_cls_layer", "cls_hidden_dim", "separate_head", "norm_cfg"]:
-            assert cfg.model[head][key] == own.model[head][key], (head, key)
-    assert cfg.model.refined_obj_head[0].test_cfg == own.model.refined_obj_head[0].test_cfg
-    assert cfg.model.frustum_obj_head.test_cfg == own.model.frustum_obj_head.test_cfg
+            assert config_digest(own.model[head][key]) == ref["heads"][head][key], (head, key)
+    assert config_digest(own.model.refined_obj_head[0].test_cfg) == ref["refined_obj_head_0_test_cfg"]
+    assert config_digest(own.model.frustum_obj_head.test_cfg) == ref["frustum_obj_head_test_cfg"]
     own_model = plugin.build_model(own.model)
-    ref_sd, own_sd = model.state_dict(), own_model.state_dict()
-    assert {k: tuple(v.shape) for k, v in ref_sd.items()} == {k: tuple(v.shape) for k, v in own_sd.items()}
-    assert model.num_extra_stages == own_model.num_extra_stages == 1
-    assert sum(p.numel() for p in model.parameters()) > 80e6  # the full detector, refine stage and heads included
+    assert state_shapes_digest(own_model) == (ref["state_dict_entries"], ref["state_dict_shapes"])
+    assert ref["num_extra_stages"] == own_model.num_extra_stages == 1
+    assert ref["parameters"] == sum(p.numel() for p in own_model.parameters()) > 80e6  # the full detector, refine stage and heads included
 
 
-REF_AV2 = "/root/reference/projects/configs/Argoverse2/FSF_AV2_config.py"
-
-
-@pytest.mark.skipif(not os.path.exists(REF_AV2), reason="reference tree only exists in the build container")
 def test_reference_av2_config_resolves():
-    cfg = Config.fromfile(REF_AV2)
-    assert cfg.model.is_argo is True and cfg.model.num_cams == 7
-    assert not unresolved(cfg.to_dict()), unresolved(cfg.to_dict())
-    seg = plugin.registry.build_detector(cfg.model.segmentor)
-    assert seg.backbone.sparse_shape == [32, 2048, 2048]
-    assert seg.voxel_layer.grid_size.tolist() == [2048, 2048, 32]
-    # the repository's own AV2 model file describes the same model (parameters and inference-relevant arguments)
+    """The reference's FSF_AV2_config.py, as recorded by tests/golden/make_golden.py::gen_reference_configs: every `type=` resolves,
+    and the repository's own AV2 model file describes the same model (parameters and inference-relevant arguments)."""
+    ref = REF_FACTS["av2"]
+    assert not unresolved_types(ref["types"]), unresolved_types(ref["types"])
     own = Config.fromfile(os.path.join(ROOT, "configs", "fsf_av2.py"))
+    assert own.model.is_argo is True and own.model.num_cams == 7
     for key in ["segmentor", "backbone", "frustum_sir", "cluster_assigner", "test_cfg", "mlp_cfg", "bbox_coder", "roi_extractor",
                 "single_refine_sir_layer", "refine_encode_2d_mlp_cfg", "encode_2d_mlp_cfg", "segmentor_updated_mlp", "is_argo",
                 "num_cams", "num_classes"]:
-        assert cfg.model[key] == own.model[key], key
-    ref_model = plugin.build_model(cfg.model, train_cfg=cfg.get("train_cfg"), test_cfg=cfg.get("test_cfg"))
+        assert config_digest(own.model[key]) == ref["model"][key], key
+    seg = plugin.registry.build_detector(own.model.segmentor)  # (the same segmentor section as the reference's: digest above)
+    assert seg.backbone.sparse_shape == [32, 2048, 2048]
+    assert seg.voxel_layer.grid_size.tolist() == [2048, 2048, 32]
     own_model = plugin.build_model(own.model)
-    assert {k: tuple(v.shape) for k, v in ref_model.state_dict().items()} == \
-           {k: tuple(v.shape) for k, v in own_model.state_dict().items()}
+    assert state_shapes_digest(own_model) == (ref["state_dict_entries"], ref["state_dict_shapes"])
     assert own_model.bbox_coder.code_size == 8 and own_model.is_argo
 
 
