@@ -19,6 +19,10 @@ _P = c_p
 _ARGTYPES = {
     "fsf_assemble_sweeps_workspace_bytes": [c_i64],
     "fsf_assemble_sweeps": [_P, c_i64, c_i32, _P, c_i32, _P, _P, _P, c_f32, _P, c_i32, c_f32, c_f32, _P, _P, _P, _P, c_i64, _P],
+    "fsf_augment_max": [],
+    "fsf_augment_points_workspace_bytes": [c_i64, c_i32],
+    "fsf_augment_points": [_P, c_i64, c_i32, _P, c_i32, _P, _P, _P, _P, _P, c_i64, _P],
+    "fsf_aug_boxes_map_back": [_P, c_i64, c_i32, _P, _P, _P, c_i64, _P, c_i32, c_i32, _P, _P, _P, _P],
     "fsf_voxelize_dynamic": [_P, c_i64, c_i32, c_i32, _P, _P, _P, _P, _P, _P],
     "fsf_vfe_decorate": [_P, c_i64, c_i32, c_i32, _P, c_i32, _P, _P, _P, _P, c_i32, c_i32, _P, c_i32, _P],
     "fsf_vote_centers_keys": [_P, c_i32, _P, c_i32, _P, c_i32, _P, _P, _P, c_i64, c_i32, c_i32, _P, _P, _P, c_i32, _P, _P, _P, _P],
@@ -198,6 +202,55 @@ def assemble_sweeps(raw: torch.Tensor, offsets, params, transform, remove_close,
                                 float(norm_std), ptr(out), None, ctypes.cast(ctypes.pointer(count), c_p), ptr(ws), ws.numel(),
                                 stream_ptr()), "fsf_assemble_sweeps")
     return out[: int(count.value)]
+
+
+def augment_max() -> int:
+    return int(_L().fsf_augment_max())
+
+
+def augment_points(points: torch.Tensor, aug_desc, pc_range=None):
+    """fsf_augment_points (K33a): points f32 [n, C] (an assembled cloud: xyz | features | no-aug xyz) + A host descriptors
+    (cos, sin, scale, angle, rotate, flip_h, flip_v) -> a list of A f32 [n_k, C] clouds, each rotated / scaled / flipped, range
+    filtered on the augmented xyz and compacted in source order.  One launch; one host wait (the A + 1 offsets)."""
+    require_cuda(points)
+    assert points.dtype == torch.float32 and points.dim() == 2 and points.size(1) >= 3
+    points = points.contiguous()
+    n, cols = points.shape
+    a = len(aug_desc)
+    out = torch.empty((max(n * a, 1), cols), dtype=torch.float32, device=points.device)
+    offsets = torch.empty((a + 1,), dtype=torch.int64, device=points.device)
+    host = (ctypes.c_int64 * (a + 1))()
+    h = _L()
+    ws = _lib.workspace(h.fsf_augment_points_workspace_bytes(n, a), points.device)
+    desc = (ctypes.c_float * (7 * a))(*[float(v) for d in aug_desc for v in d])
+    check(h.fsf_augment_points(ptr(points), n, cols, desc, a, _lib.f32_array(pc_range) if pc_range is not None else c_p(None),
+                               ptr(out), ptr(offsets), ctypes.cast(host, c_p), ptr(ws), ws.numel(), stream_ptr()),
+          "fsf_augment_points")
+    return [out[int(host[k]): int(host[k + 1])] for k in range(a)]
+
+
+def aug_boxes_map_back(boxes: torch.Tensor, scores: torch.Tensor, labels: torch.Tensor, pass_idx: torch.Tensor, pass_desc,
+                       num_classes: int):
+    """fsf_aug_boxes_map_back (K33b): concatenated per-pass boxes f32 [m, 7 | 9], scores f32 [m], labels i64 [m], pass index
+    i32 [m] + per-pass host descriptors (scale = fp32(1 / s)) -> (boxes f32 [m, D] in the un-augmented frame, boxes_nms f32 [m, 5],
+    scores_t f32 [num_classes, m]).  No sync."""
+    require_cuda(boxes, scores, labels, pass_idx)
+    assert boxes.dtype == torch.float32 and scores.dtype == torch.float32 and labels.dtype == torch.int64
+    assert pass_idx.dtype == torch.int32 and boxes.dim() == 2
+    boxes, d = _rows_view(boxes)
+    scores, labels, pass_idx = scores.contiguous(), labels.contiguous(), pass_idx.contiguous()
+    m, dim = boxes.size(0), boxes.size(1)
+    assert scores.numel() == m and labels.numel() == m and pass_idx.numel() == m
+    dev = boxes.device
+    out = torch.empty((m, dim), dtype=torch.float32, device=dev)
+    nms = torch.empty((m, 5), dtype=torch.float32, device=dev)
+    scores_t = torch.empty((int(num_classes), m), dtype=torch.float32, device=dev)
+    p = len(pass_desc)
+    desc = (ctypes.c_float * (7 * p))(*[float(v) for dd in pass_desc for v in dd])
+    check(_L().fsf_aug_boxes_map_back(c_p(boxes.data_ptr()) if m else c_p(None), d, dim, ptr(scores), ptr(labels), ptr(pass_idx), m,
+                                      desc, p, int(num_classes), ptr(out), ptr(nms), ptr(scores_t), stream_ptr()),
+          "fsf_aug_boxes_map_back")
+    return out, nms, scores_t
 
 
 def voxelize_dynamic(points: torch.Tensor, voxel_size, pc_range, grid, batch_idx: int = 0, want_zyx=True,

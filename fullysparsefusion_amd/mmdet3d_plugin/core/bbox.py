@@ -7,6 +7,7 @@
   from their published behaviour.  The NMS itself is the HIP kernel pair behind `fsf_nms_bev` (K20): the greedy scan
   stays on the device instead of mmdet3d's bitmask-to-host round trip.
 """
+import numpy as np
 import torch
 
 from ... import hip_ops
@@ -218,3 +219,193 @@ def bbox3d2result(bboxes, scores, labels, attrs=None):
     if attrs is not None:
         result["attrs_3d"] = attrs.cpu()
     return result
+
+
+# ------------------------------------------------------------------------------ test-time augmentation (K33)
+def _bev_corners(b):
+    """xyxyr [n, 5] (float64) -> [n, 4, 2]: the corners iou3d rotates (`rotate_around_center`: by -yaw about the centre)."""
+    cx, cy = (b[:, 0] + b[:, 2]) / 2, (b[:, 1] + b[:, 3]) / 2
+    c, s = torch.cos(b[:, 4]), torch.sin(b[:, 4])
+    out = []
+    for ix, iy in ((0, 1), (2, 1), (2, 3), (0, 3)):
+        dx, dy = b[:, ix] - cx, b[:, iy] - cy
+        out.append(torch.stack([dx * c + dy * s + cx, -dx * s + dy * c + cy], -1))
+    return torch.stack(out, 1)
+
+
+def _clip_area(p, q):
+    """Area of the intersection of two convex quadrilaterals (lists of (x, y); Sutherland-Hodgman)."""
+    def area(poly):
+        return 0.5 * abs(sum(poly[i][0] * poly[i - 1][1] - poly[i - 1][0] * poly[i][1] for i in range(len(poly))))
+
+    orient = 1.0 if sum(q[i - 1][0] * q[i][1] - q[i][0] * q[i - 1][1] for i in range(4)) > 0 else -1.0
+    out = list(p)
+    for i in range(4):
+        a, b = q[i - 1], q[i]
+        side = lambda v: orient * ((b[0] - a[0]) * (v[1] - a[1]) - (b[1] - a[1]) * (v[0] - a[0]))  # noqa: E731
+        inp, out = out, []
+        for j in range(len(inp)):
+            cur, prev = inp[j], inp[j - 1]
+            sc, sp = side(cur), side(prev)
+            if sc >= 0:
+                if sp < 0:
+                    t = sp / (sp - sc)
+                    out.append((prev[0] + t * (cur[0] - prev[0]), prev[1] + t * (cur[1] - prev[1])))
+                out.append(cur)
+            elif sp >= 0:
+                t = sp / (sp - sc)
+                out.append((prev[0] + t * (cur[0] - prev[0]), prev[1] + t * (cur[1] - prev[1])))
+        if not out:
+            return 0.0
+    return area(out)
+
+
+def bev_iou_host(a, b, rotated=True):
+    """BEV IoU of xyxyr rows a [n, 5] and b [m, 5] in float64 on the host (the overlap iou3d's nms_gpu / nms_normal_gpu test)."""
+    a, b = a.detach().double().cpu(), b.detach().double().cpu()
+    area_a = (a[:, 2] - a[:, 0]) * (a[:, 3] - a[:, 1])
+    area_b = (b[:, 2] - b[:, 0]) * (b[:, 3] - b[:, 1])
+    if not rotated:
+        w = (torch.minimum(a[:, None, 2], b[None, :, 2]) - torch.maximum(a[:, None, 0], b[None, :, 0])).clamp(min=0)
+        h = (torch.minimum(a[:, None, 3], b[None, :, 3]) - torch.maximum(a[:, None, 1], b[None, :, 1])).clamp(min=0)
+        inter = w * h
+    else:
+        ca, cb = _bev_corners(a).tolist(), _bev_corners(b).tolist()
+        inter = torch.tensor([[_clip_area(p, q) for q in cb] for p in ca], dtype=torch.float64).reshape(len(ca), len(cb))
+    return inter / (area_a[:, None] + area_b[None, :] - inter).clamp(min=1e-8)
+
+
+def _nms_host(boxes_xyxyr, scores, thresh, rotated):
+    """Greedy NMS on the host: stable descending score order (ties: ascending index), suppress IoU > thresh."""
+    order = scores.sort(descending=True, stable=True)[1]
+    b = boxes_xyxyr[order]
+    iou = bev_iou_host(b, b, rotated)
+    removed = torch.zeros(len(order), dtype=torch.bool)
+    keep = []
+    for i in range(len(order)):
+        if removed[i]:
+            continue
+        keep.append(i)
+        removed[i + 1:] |= iou[i, i + 1:] > thresh
+    return order[torch.tensor(keep, dtype=torch.long)]
+
+
+def bbox3d_mapping_back(bboxes, scale_factor, flip_horizontal, flip_vertical, rot_factor=0.0):
+    """mmdet3d's bbox3d_mapping_back [UNVENDORED mmdet3d.core.bbox.transforms] plus the rotation the reference's TTA adds: undo
+    the vertical flip, the horizontal flip, the scale (x fp32(1 / s)), then the rotation (centre and velocity by -angle, yaw + angle:
+    this box convention turns yaw clockwise).  fp32, the arithmetic of K33b (csrc/augment.hip)."""
+    from ..datasets.pipelines import augmentation_descriptor
+
+    t = getattr(bboxes, "tensor", bboxes).clone()
+    c, s, inv, angle, rot, _, _ = augmentation_descriptor(rot_factor, scale_factor, flip_horizontal, flip_vertical, inverse=True)
+    vel = t.size(1) >= 9
+    if flip_vertical:
+        t[:, 0] = -t[:, 0]
+        if vel:
+            t[:, 7] = -t[:, 7]
+        t[:, 6] = -t[:, 6]
+    if flip_horizontal:
+        t[:, 1] = -t[:, 1]
+        if vel:
+            t[:, 8] = -t[:, 8]
+        t[:, 6] = -t[:, 6] + float(np.float32(np.pi))
+    t[:, :6] *= inv
+    t[:, 7:] *= inv
+    if rot:
+        for i, j in ((0, 1), (7, 8)) if vel else ((0, 1),):
+            x, y = t[:, i].clone(), t[:, j].clone()
+            t[:, i] = (x * c) + (y * s)
+            t[:, j] = (y * c) - (x * s)
+        t[:, 6] = t[:, 6] + angle
+    if isinstance(bboxes, LiDARInstance3DBoxes):
+        return type(bboxes)(t, box_dim=t.size(1), with_yaw=bboxes.with_yaw)
+    return t
+
+
+def _meta0(meta):
+    return meta[0] if isinstance(meta, (list, tuple)) else meta
+
+
+def merge_aug_bboxes_3d(aug_results, img_metas, test_cfg):
+    """mmdet3d's merge_aug_bboxes_3d [UNVENDORED mmdet3d.core.post_processing.merge_augs] on the host — the readable spec of
+    `merge_aug_bboxes_3d_device` and the route for CPU tensors / configurations the device path does not take.
+      aug_results  one bbox3d2result dict per pass (boxes_3d, scores_3d, labels_3d) in the pass's augmented frame;
+      img_metas    one meta dict (or mmdet3d's one-element list of it) per pass: pcd_scale_factor, pcd_horizontal_flip,
+                   pcd_vertical_flip, pcd_rot_factor (absent: 0);
+      test_cfg     nms_thr, use_rotate_nms, max_num.
+    Every pass's boxes are mapped back (`bbox3d_mapping_back`), concatenated, class-wise BEV NMS'ed (class by class, ascending
+    class id), then sorted by descending score and cut to max_num.  Ties: both sorts are stable, so equal scores keep
+    class-major order and, inside a class, concatenation (pass, then row) order — mmdet3d's unstable sort leaves them open."""
+    assert len(aug_results) == len(img_metas)
+    get = test_cfg.get if isinstance(test_cfg, dict) else lambda k, d=None: getattr(test_cfg, k, d)
+    boxes, scores, labels, box_dim = [], [], [], None
+    for res, meta in zip(aug_results, img_metas):
+        m = _meta0(meta)
+        t = getattr(res["boxes_3d"], "tensor", res["boxes_3d"])
+        if len(t) == 0:
+            continue
+        box_dim = t.size(1)
+        boxes.append(bbox3d_mapping_back(t.float().cpu(), m.get("pcd_scale_factor", 1.0), m.get("pcd_horizontal_flip", False),
+                                         m.get("pcd_vertical_flip", False), m.get("pcd_rot_factor", 0.0)))
+        scores.append(res["scores_3d"].float().cpu())
+        labels.append(res["labels_3d"].long().cpu())
+    if not boxes:
+        t0 = getattr(aug_results[0]["boxes_3d"], "tensor", aug_results[0]["boxes_3d"])
+        d = t0.size(1) if t0.dim() == 2 else 7
+        return dict(boxes_3d=LiDARInstance3DBoxes(torch.zeros((0, d)), box_dim=d), scores_3d=torch.zeros(0),
+                    labels_3d=torch.zeros(0, dtype=torch.long))
+    aug_boxes, aug_scores, aug_labels = torch.cat(boxes), torch.cat(scores), torch.cat(labels)
+    for_nms = xywhr2xyxyr(aug_boxes[:, [0, 1, 3, 4, 6]])
+    rotated = bool(get("use_rotate_nms", False))
+    mb, ms, ml = [], [], []
+    for class_id in range(int(aug_labels.max()) + 1):
+        idx = (aug_labels == class_id).nonzero(as_tuple=True)[0]
+        if len(idx) == 0:
+            continue
+        sel = idx[_nms_host(for_nms[idx], aug_scores[idx], float(get("nms_thr")), rotated)]
+        mb.append(aug_boxes[sel])
+        ms.append(aug_scores[sel])
+        ml.append(aug_labels[sel])
+    mb, ms, ml = torch.cat(mb), torch.cat(ms), torch.cat(ml)
+    order = ms.sort(descending=True, stable=True)[1][: min(int(get("max_num")), len(aug_boxes))]
+    return dict(boxes_3d=LiDARInstance3DBoxes(mb[order].contiguous(), box_dim=box_dim), scores_3d=ms[order].contiguous(),
+                labels_3d=ml[order].contiguous())
+
+
+def merge_aug_bboxes_3d_device(boxes, scores, labels, pass_idx, img_metas, test_cfg, num_classes):
+    """`merge_aug_bboxes_3d` on the device, for the concatenated per-pass results (boxes f32 [m, 7 | 9], scores f32 [m], labels
+    i64 [m], pass index i32 [m]): K33b (map back + NMS form + class-major scores), K24's class ranks, K20's capped class-wise NMS,
+    K24's selection, a stable score sort of the <= max_num rows — and ONE read-back.  Returns the bbox3d2result dict (host)."""
+    from ..datasets.pipelines import meta_descriptor
+
+    get = test_cfg.get if isinstance(test_cfg, dict) else lambda k, d=None: getattr(test_cfg, k, d)
+    max_num = int(get("max_num"))
+    d = boxes.size(1)
+    descs = [meta_descriptor(_meta0(m), inverse=True) for m in img_metas]
+    out, for_nms, scores_t = hip_ops.aug_boxes_map_back(boxes, scores, labels, pass_idx, descs, num_classes)
+    order, rank, count = hip_ops.class_rank_desc(scores_t, float("-inf"))
+    keep, num, incomplete = hip_ops.nms_bev_multiclass(for_nms, rank, count, float(get("nms_thr")),
+                                                       rotated=bool(get("use_rotate_nms", False)), max_keep=max_num, windowed=True)
+    buf = hip_ops.nms_select(out, scores_t, order, keep, num, max_num, max_num, None, incomplete)
+    w = d + 2
+    rows = buf[: max_num * w].view(max_num, w)
+    meta = buf[max_num * w:].view(torch.int32)
+    valid = torch.arange(max_num, device=buf.device) < meta[0]
+    key = torch.where(valid, rows[:, d], rows.new_full((), float("-inf")))
+    rows = rows[key.sort(descending=True, stable=True)[1]]  # (nms_select: class-major when <= max_num kept; merge: by score)
+    host = torch.cat([rows.reshape(-1), buf[max_num * w:]]).cpu()  # the merge's one read-back
+    hm = host[max_num * w:].view(torch.int32)
+    if int(hm[2]) != 0:  # a class ran out of its mask window before max_num keeps: full masks (never expected at TTA sizes)
+        keep, num = hip_ops.nms_bev_multiclass(for_nms, rank, count, float(get("nms_thr")), rotated=bool(get("use_rotate_nms", False)),
+                                               max_keep=max_num)
+        buf = hip_ops.nms_select(out, scores_t, order, keep, num, max_num, max_num, None, None)
+        rows = buf[: max_num * w].view(max_num, w)
+        valid = torch.arange(max_num, device=buf.device) < buf[max_num * w:].view(torch.int32)[0]
+        key = torch.where(valid, rows[:, d], rows.new_full((), float("-inf")))
+        rows = rows[key.sort(descending=True, stable=True)[1]]
+        host = torch.cat([rows.reshape(-1), buf[max_num * w:]]).cpu()
+        hm = host[max_num * w:].view(torch.int32)
+    k = int(hm[0])
+    r = host[: max_num * w].view(max_num, w)[:k]
+    return dict(boxes_3d=LiDARInstance3DBoxes._wrap(r[:, :d].contiguous(), d), scores_3d=r[:, d].contiguous(),
+                labels_3d=r[:, d + 1].long())

@@ -282,35 +282,110 @@ class NormalizePoints:
         return input_dict
 
 
+def rotation_cos_sin(angle):
+    """cos / sin of the fp32 angle, as mmdet3d computes them (`torch.sin(points.tensor.new_tensor(angle))`)."""
+    a = torch.tensor(float(angle), dtype=torch.float32)
+    return float(torch.cos(a)), float(torch.sin(a))
+
+
+def rotate_xyz_(t, angle):
+    """Rotate the xyz columns of the f32 tensor `t` about z in place, counter-clockwise by `angle` (the sign relative to the reference's
+    `pcd_rot_factor`: DESIGN.md section 3, "Rotation sign").  The arithmetic is pinned: x' = x c - y s, y' = x s + y c with each
+    product and the sum rounded on its own — where a matrix form `xyz @ rot_mat_T` leaves the rounding to the sgemm (<= 1 ulp apart) —
+    so that K33a (csrc/augment.hip) reproduces it bit for bit.  Returns rot_mat_T (xyz @ rot_mat_T is the same rotation)."""
+    c, s = rotation_cos_sin(angle)
+    x, y = t[:, 0].clone(), t[:, 1].clone()
+    t[:, 0] = (x * c) - (y * s)
+    t[:, 1] = (x * s) + (y * c)
+    return torch.tensor([[c, s, 0.0], [-s, c, 0.0], [0.0, 0.0, 1.0]], dtype=torch.float32)
+
+
+def augmentation_descriptor(rot_factor=0.0, scale_factor=1.0, flip_horizontal=False, flip_vertical=False, inverse=False):
+    """The 7 floats K33a / K33b take per augmentation: (cos, sin, scale, angle, rotate, flip_h, flip_v).  `inverse` (K33b, mapping
+    boxes back): scale = fp32(1 / s), mmdet3d's `boxes.scale(1 / scale_factor)`."""
+    angle = float(np.float32(rot_factor))
+    c, s = rotation_cos_sin(angle)
+    scale = float(np.float32(1.0 / float(scale_factor))) if inverse else float(np.float32(scale_factor))
+    return (c, s, scale, angle, float(angle != 0.0), float(bool(flip_horizontal)), float(bool(flip_vertical)))
+
+
+def meta_descriptor(meta, inverse=False):
+    """`augmentation_descriptor` of one pass from its img_metas: the flags the pipeline recorded, never re-derived."""
+    return augmentation_descriptor(meta.get("pcd_rot_factor", 0.0), meta.get("pcd_scale_factor", 1.0),
+                                   meta.get("pcd_horizontal_flip", False), meta.get("pcd_vertical_flip", False), inverse)
+
+
 @PIPELINES.register_module(force=True)
 class GlobalRotScaleTrans:
-    """Test-time identity only (rot_range [0, 0], scale [1, 1], translation_std 0 — the values the test pipelines pass)."""
+    """Test-time global rotation -> scale -> translation with PRESET factors (MyGlobalRotScaleTrans, transforms_3d.py:15-180):
+    `pcd_rot_factor` / `pcd_scale_factor` set by (My)MultiScaleFlipAug3D.  Without a preset factor only the identity ranges of the
+    test pipelines (rot_range [0, 0], scale [1, 1]) are accepted; translation std must be 0.  Random train-time draws raise."""
 
     def __init__(self, rot_range=[-0.78539816, 0.78539816], scale_ratio_range=[0.95, 1.05], translation_std=[0, 0, 0],
                  shift_height=False):
-        ts = translation_std if isinstance(translation_std, (list, tuple)) else [translation_std] * 3
-        self.identity = list(rot_range) == [0, 0] and list(scale_ratio_range) == [1.0, 1.0] and all(t == 0 for t in ts)
+        if not isinstance(rot_range, (list, tuple, np.ndarray)):
+            rot_range = [-rot_range, rot_range]
+        ts = translation_std if isinstance(translation_std, (list, tuple, np.ndarray)) else [translation_std] * 3
+        self.rot_range, self.scale_ratio_range = [float(v) for v in rot_range], [float(v) for v in scale_ratio_range]
+        self.translation_std, self.shift_height = [float(v) for v in ts], shift_height
 
     def __call__(self, input_dict):
-        if not self.identity:
-            raise NotImplementedError("train-time GlobalRotScaleTrans augmentation is outside the built path")
-        input_dict.update(pcd_rotation=torch.eye(3), pcd_scale_factor=1.0, pcd_trans=np.zeros(3, dtype=np.float32))
+        if "pcd_rot_factor" in input_dict:
+            angle = float(input_dict["pcd_rot_factor"])
+        elif self.rot_range == [0.0, 0.0]:
+            angle = 0.0
+        else:
+            raise NotImplementedError("train-time GlobalRotScaleTrans augmentation (random rotation) is outside the built path")
+        if "pcd_scale_factor" in input_dict:
+            scale = float(input_dict["pcd_scale_factor"])
+        elif self.scale_ratio_range == [1.0, 1.0]:
+            scale = 1.0
+        else:
+            raise NotImplementedError("train-time GlobalRotScaleTrans augmentation (random scale) is outside the built path")
+        if any(t != 0 for t in self.translation_std) or self.shift_height:
+            raise NotImplementedError("train-time GlobalRotScaleTrans augmentation (translation noise) is outside the built path")
+        points = input_dict.get("points")
+        rot_mat_T = torch.eye(3)
+        if points is not None and angle != 0.0:
+            rot_mat_T = rotate_xyz_(points.tensor, angle)
+        if points is not None and scale != 1.0:
+            points.tensor[:, :3] *= scale
+        input_dict.update(pcd_rotation=rot_mat_T, pcd_rot_factor=angle, pcd_scale_factor=scale, pcd_trans=np.zeros(3, dtype=np.float32))
         return input_dict
 
 
 @PIPELINES.register_module(force=True)
 class RandomFlip3D:
-    """Inside MultiScaleFlipAug3D(flip=False) the flip flags arrive preset to False: nothing to flip."""
+    """Test-time BEV flips with PRESET flags: horizontal (y -> -y) first, then vertical (x -> -x).  mmdet3d's sync_2d (default
+    True) makes the horizontal flag follow the image `flip` flag and clears the vertical one; with sync_2d=False the flags
+    MultiScaleFlipAug3D preset are used as they are.  A random flip (a ratio with no preset flag) raises."""
 
     def __init__(self, sync_2d=True, flip_ratio_bev_horizontal=0.0, flip_ratio_bev_vertical=0.0, **kwargs):
+        self.sync_2d = sync_2d
         self.ratios = (flip_ratio_bev_horizontal, flip_ratio_bev_vertical)
 
     def __call__(self, input_dict):
-        if input_dict.get("pcd_horizontal_flip", False) or input_dict.get("pcd_vertical_flip", False) or any(self.ratios):
-            raise NotImplementedError("train-time RandomFlip3D augmentation is outside the built path")
-        input_dict.setdefault("pcd_horizontal_flip", False)
-        input_dict.setdefault("pcd_vertical_flip", False)
+        if self.sync_2d:
+            if "flip" not in input_dict and self.ratios[0]:
+                raise NotImplementedError("train-time RandomFlip3D augmentation is outside the built path")
+            input_dict["pcd_horizontal_flip"] = bool(input_dict.get("flip", False))
+            input_dict["pcd_vertical_flip"] = False
+        else:
+            for key, ratio in zip(("pcd_horizontal_flip", "pcd_vertical_flip"), self.ratios):
+                if key not in input_dict:
+                    if ratio:
+                        raise NotImplementedError("train-time RandomFlip3D augmentation is outside the built path")
+                    input_dict[key] = False
+        points = input_dict.get("points")
+        if points is not None and input_dict["pcd_horizontal_flip"]:
+            points.tensor[:, 1] = -points.tensor[:, 1]
+        if points is not None and input_dict["pcd_vertical_flip"]:
+            points.tensor[:, 0] = -points.tensor[:, 0]
         return input_dict
+
+
+PIPELINES.register_module("MyGlobalRotScaleTrans", force=True, module=GlobalRotScaleTrans)
+MyGlobalRotScaleTrans = GlobalRotScaleTrans
 
 
 @PIPELINES.register_module(force=True)
@@ -328,7 +403,7 @@ class DefaultFormatBundle3D:
 class Collect3D:
     META = ("filename", "ori_shape", "img_shape", "lidar2img", "depth2img", "cam2img", "pad_shape", "scale_factor", "flip",
             "pcd_horizontal_flip", "pcd_vertical_flip", "box_mode_3d", "box_type_3d", "img_norm_cfg", "pcd_trans", "sample_idx",
-            "pcd_scale_factor", "pcd_rotation", "pts_filename", "transformation_3d_flow")
+            "pcd_scale_factor", "pcd_rotation", "pcd_rot_factor", "pts_filename", "transformation_3d_flow")
 
     def __init__(self, keys, meta_keys=META):
         self.keys, self.meta_keys = keys, meta_keys
@@ -352,26 +427,84 @@ class Compose:
         return data
 
 
+def _as_list(v, cast=None):
+    v = v if isinstance(v, list) else [v]
+    return [cast(x) for x in v] if cast else v
+
+
+def _aug_dict_of_lists(aug_data):
+    out = {key: [] for key in aug_data[0]}
+    for data in aug_data:
+        for key, val in data.items():
+            out[key].append(val)
+    return out
+
+
 @PIPELINES.register_module(force=True)
 class MultiScaleFlipAug3D:
-    """mmdet3d test-time wrapper; the FSF configs use one scale and no flip, so it wraps every collected value in a
-    one-element list (the `num_augs == 1` form `FSF.forward_test` expects, FSF.py:1096-1112)."""
+    """mmdet3d's test-time wrapper: one pipeline run per (image scale, point scale, flip, horizontal pcd flip, vertical pcd flip,
+    flip direction), each on a deep copy of the input (one augmentation: a shallow copy, as before); returns a dict of lists (one entry per augmentation, the form
+    `FSF.forward_test` takes).  flip=True enumerates flip in [False, True] (so the pcd flips appear twice, once per image flip
+    flag)."""
+
+    FLIP_AUG = (False, True)
 
     def __init__(self, transforms, img_scale, pts_scale_ratio, flip=False, flip_direction="horizontal",
                  pcd_horizontal_flip=False, pcd_vertical_flip=False):
-        scales = pts_scale_ratio if isinstance(pts_scale_ratio, list) else [pts_scale_ratio]
-        if flip or pcd_horizontal_flip or pcd_vertical_flip or len(scales) != 1 or float(scales[0]) != 1.0:
-            raise NotImplementedError("test-time augmentation (multi-scale / flip) is outside the built path")
         self.transforms = Compose(transforms)
+        self.img_scale = _as_list(img_scale)
+        self.pts_scale_ratio = _as_list(pts_scale_ratio, float)
+        self.pts_rot_ratio = [None]
+        self.flip, self.pcd_horizontal_flip, self.pcd_vertical_flip = flip, pcd_horizontal_flip, pcd_vertical_flip
+        self.flip_direction = _as_list(flip_direction)
+
+    def _flip_aug(self):
+        return list(self.FLIP_AUG) if self.flip else [False]
 
     def __call__(self, results):
-        res = dict(results)
-        res.update(scale=None, flip=False, pcd_scale_factor=1.0, pcd_horizontal_flip=False, pcd_vertical_flip=False)
-        data = self.transforms(res)
-        return {k: [v] for k, v in data.items()}
+        from copy import deepcopy
+
+        aug_data = []
+        h_aug = [False, True] if self.flip and self.pcd_horizontal_flip else [False]
+        v_aug = [False, True] if self.flip and self.pcd_vertical_flip else [False]
+        single = (len(self.img_scale) * len(self.pts_scale_ratio) * len(self.pts_rot_ratio) * len(self._flip_aug()) * len(h_aug) * len(v_aug)
+                  * len(self.flip_direction)) == 1
+        for scale in self.img_scale:
+            for pts_scale_ratio in self.pts_scale_ratio:
+                for pts_rot_ratio in self.pts_rot_ratio:
+                    for flip in self._flip_aug():
+                        for pcd_horizontal_flip in h_aug:
+                            for pcd_vertical_flip in v_aug:
+                                for direction in self.flip_direction:
+                                    # (a shallow copy would share the point tensor between passes; one pass has nothing to share it
+                                    # with, and a deep copy would duplicate the ~86 MB of id planes loaded before the wrapper)
+                                    _results = dict(results) if single else deepcopy(results)
+                                    _results["scale"] = scale
+                                    _results["flip"] = flip
+                                    _results["pcd_scale_factor"] = pts_scale_ratio
+                                    if pts_rot_ratio is not None:
+                                        _results["pcd_rot_factor"] = pts_rot_ratio
+                                    _results["flip_direction"] = direction
+                                    _results["pcd_horizontal_flip"] = pcd_horizontal_flip
+                                    _results["pcd_vertical_flip"] = pcd_vertical_flip
+                                    aug_data.append(self.transforms(_results))
+        return _aug_dict_of_lists(aug_data)
 
 
-PIPELINES.register_module("MyMultiScaleFlipAug3D", force=True, module=MultiScaleFlipAug3D)
+@PIPELINES.register_module(force=True)
+class MyMultiScaleFlipAug3D(MultiScaleFlipAug3D):
+    """The reference's wrapper (projects/mmdet3d_plugin/datasets/pipelines/test_time_aug.py:78-113): a `pts_rot_ratio` loop
+    (preset `pcd_rot_factor` for MyGlobalRotScaleTrans) between the point scales and the flips, and flip=True enumerates the
+    image flip as [True] only.  Order: image scale -> point scale -> rotation -> flip -> horizontal -> vertical -> direction."""
+
+    FLIP_AUG = (True,)
+
+    def __init__(self, transforms, img_scale, pts_scale_ratio, pts_rot_ratio, flip=False, flip_direction="horizontal",
+                 pcd_horizontal_flip=False, pcd_vertical_flip=False):
+        super().__init__(transforms, img_scale, pts_scale_ratio, flip, flip_direction, pcd_horizontal_flip, pcd_vertical_flip)
+        self.pts_rot_ratio = _as_list(pts_rot_ratio, float)
+
+
 PIPELINES.register_module("MyPointsRangeFilter", force=True, module=PointsRangeFilter)
 
 
@@ -384,8 +517,13 @@ class DevicePointAssembler:
     the host classes above).  Returns f32 [N, load_dim + 3] on `device`: what `FSF.simple_test` takes as `points[0]`."""
 
     def __init__(self, load_dim=5, sweeps_num=9, pad_empty_sweeps=True, remove_close=True, test_mode=False,
-                 point_cloud_range=None, norm_dims=(3,), norm_mean=(0,), norm_std=(255,), close_radius=1.0):
+                 point_cloud_range=None, norm_dims=(3,), norm_mean=(0,), norm_std=(255,), close_radius=1.0, augmentations=None):
+        """augmentations: None (one cloud, as before) or a list of dicts with the preset factors of each test-time augmentation
+        (pcd_rot_factor, pcd_scale_factor, pcd_horizontal_flip, pcd_vertical_flip; absent = identity): then K0 runs without its
+        range filter and K33a (`fsf_augment_points`) makes the A augmented, range-filtered clouds from the one upload — the call
+        returns their list, what (My)MultiScaleFlipAug3D's per-augmentation pipelines produce after their upload."""
         assert len(norm_dims) <= 1, "the kernel normalises one column (the reference configs use dims=[3])"
+        self.augmentations = None if augmentations is None else [dict(a) for a in augmentations]
         self.load_dim, self.sweeps_num = load_dim, sweeps_num
         self.pad_empty_sweeps, self.remove_close, self.test_mode = pad_empty_sweeps, remove_close, test_mode
         self.point_cloud_range = None if point_cloud_range is None else [float(v) for v in point_cloud_range]
@@ -426,8 +564,13 @@ class DevicePointAssembler:
         if torch.cuda.is_available():
             raw = raw.pin_memory()
         col, mean, std = self.norm
-        return hip_ops.assemble_sweeps(raw.to(device, non_blocking=True), offsets, params, transform, close, self.close_radius,
-                                       self.point_cloud_range, col, mean, std)
+        if self.augmentations is None:
+            return hip_ops.assemble_sweeps(raw.to(device, non_blocking=True), offsets, params, transform, close, self.close_radius,
+                                           self.point_cloud_range, col, mean, std)
+        # (the intensity normalisation touches no xyz column: it commutes with the augmentation; the range test must not)
+        cloud = hip_ops.assemble_sweeps(raw.to(device, non_blocking=True), offsets, params, transform, close, self.close_radius, None,
+                                        col, mean, std)
+        return hip_ops.augment_points(cloud, [meta_descriptor(a) for a in self.augmentations], self.point_cloud_range)
 
 
 def frame_to_device(data, device):
@@ -442,3 +585,27 @@ def frame_to_device(data, device):
         mask = mask.to(torch.int32)
     meta["lidar2img"] = torch.as_tensor(np.asarray(meta["lidar2img"]), dtype=torch.float32).to(device)
     return ([points.float().contiguous().to(device)], [meta], mask.to(device)[None], anno.float().to(device)[None])
+
+
+def aug_frame_to_device(data, device):
+    """Pipeline output of one sample with `num_augs >= 1` (a dict of per-augmentation lists) -> the per-augmentation argument
+    lists of `FSF.forward_test` / `FSF.aug_test`.  Every augmentation's points go up on their own; the id planes, `mask_anno` and
+    each camera's lidar2img go up ONCE and are shared by every augmentation (the image side reads the no-aug xyz: it is not
+    augmented)."""
+    unwrap = lambda v: v[0] if isinstance(v, list) else v  # noqa: E731
+    mask = unwrap(data["mask_data"])
+    anno = unwrap(data["mask_anno"])
+    if mask.dtype not in (torch.uint8, torch.int32):
+        mask = mask.to(torch.int32)
+    mask_d, anno_d = mask.to(device)[None], anno.float().to(device)[None]
+    metas = data["img_metas"] if isinstance(data["img_metas"], list) else [data["img_metas"]]
+    pts = data["points"] if isinstance(data["points"], list) else [data["points"]]
+    l2i = torch.as_tensor(np.asarray(metas[0]["lidar2img"]), dtype=torch.float32).to(device)
+    points, out_metas = [], []
+    for p, m in zip(pts, metas):
+        m = dict(m)
+        m["lidar2img"] = l2i
+        points.append([p.float().contiguous().to(device)])
+        out_metas.append([m])
+    a = len(points)
+    return points, out_metas, [mask_d] * a, [anno_d] * a

@@ -27,7 +27,7 @@ import torch.nn.functional as F
 from .... import hip_ops
 from ...ops.sst_ops import (GatheredRows, RowsMinusGroup, build_mlp, clear_unique_cache, gather_by_inverse, point_linear_add, scatter_v2,
                             seed_unique_result, swap_unique_cache, unique_with_plan, with_key_bounds)
-from ...core.bbox import bbox3d2result
+from ...core.bbox import LiDARInstance3DBoxes, bbox3d2result, merge_aug_bboxes_3d, merge_aug_bboxes_3d_device
 from ...registry import BBOX_CODERS, DETECTORS, build_head, build_roi_extractor
 from .single_stage_fsd import SingleStageFSD
 
@@ -935,9 +935,56 @@ class FSF(SingleStageFSD):
         return [bbox3d2result(bboxes, scores, labels) for bboxes, scores, labels in bbox_list]
 
     def forward_test(self, points, img_metas, mask_data, mask_anno, **kwargs):
-        if len(points) != 1:
-            raise NotImplementedError("test-time augmentation is outside the hot path")
+        if len(points) > 1:  # one entry per augmentation (MultiScaleFlipAug3D / MyMultiScaleFlipAug3D): test-time augmentation
+            return self.aug_test(points, img_metas, mask_data, mask_anno, **kwargs)
         return self.simple_test(points[0], img_metas[0], mask_data[0], mask_anno[0], **kwargs)
+
+    # ------------------------------------------------------------------------------ test-time augmentation (K33)
+    def aug_test(self, points, img_metas, mask_data, mask_anno, merge_cfg=None, announce=True, **kwargs):
+        """Flip / rotation / scale TTA (the reference routes num_augs > 1 here, FSF.py:1096-1112, and never implements it): one
+        batch-1 `forward_queries` per augmentation, each pass's device boxes kept as they are, then the device merge
+        (`merge_aug_bboxes_3d_device`: K33b map-back, class-wise rotated BEV NMS, score sort, max_num) with one read-back.
+        Arguments are per-augmentation lists of `simple_test`'s (the flags come from each pass's img_metas, never re-derived).
+        Pass k announces pass k + 1 (K32), so its front runs under pass k's box tail; a caller's own `set_next_frame` is re-armed for
+        the last pass.  merge_cfg: nms_thr / use_rotate_nms / max_num over the final stage's test cfg.  Returns [bbox3d2result]."""
+        if kwargs.get("hot_path_only", False) or self.num_extra_stages == 0:
+            raise ValueError("aug_test needs the refinement stages' boxes to merge (hot_path_only / num_extra_stages == 0 return none)")
+        n = len(points)
+        assert n == len(img_metas) == len(mask_data) == len(mask_anno) and n >= 1
+        assert all(len(p) == 1 for p in points), "aug_test runs one sample (batch size 1) per augmentation"
+        head = self.frustum_refined_head[self.num_extra_stages - 1]
+        cfg = dict(head.test_cfg)
+        cfg.update(merge_cfg or {})
+        caller = self.__dict__.pop("_next_frame", None)
+        passes = []
+        try:
+            for k in range(n):
+                if k + 1 < n and announce:
+                    self.set_next_frame(points[k + 1], img_metas[k + 1], mask_data[k + 1], mask_anno[k + 1])
+                elif k + 1 == n and caller is not None:
+                    self._next_frame = caller
+                    caller = None
+                bbox_list = self.forward_queries(points[k], img_metas[k], mask_data[k], mask_anno[k])
+                boxes, scores, labels = bbox_list[0]
+                passes.append((getattr(boxes, "tensor", boxes), scores, labels))
+        finally:
+            if caller is not None:  # (a pass raised before the last one: the caller's announcement stands)
+                self._next_frame = caller
+        metas = [m[0] for m in img_metas]
+        keep = [k for k, (b, _, _) in enumerate(passes) if len(b) > 0]
+        if not keep:
+            d = passes[0][0].size(1)
+            return [dict(boxes_3d=LiDARInstance3DBoxes(torch.zeros((0, d)), box_dim=d), scores_3d=torch.zeros(0),
+                         labels_3d=torch.zeros(0, dtype=torch.long))]
+        boxes = torch.cat([passes[k][0] for k in keep])
+        scores = torch.cat([passes[k][1] for k in keep])
+        labels = torch.cat([passes[k][2].long() for k in keep])
+        pass_idx = torch.cat([torch.full((len(passes[k][0]),), k, dtype=torch.int32, device=boxes.device) for k in keep])
+        if not (boxes.is_cuda and boxes.dtype == torch.float32 and boxes.size(1) in (7, 9) and n <= hip_ops.augment_max()
+                and len(head.class_names) <= hip_ops.box_tail_max_classes()
+                and len(head.class_names) * int(cfg["max_num"]) <= hip_ops.nms_select_capacity()):
+            return [merge_aug_bboxes_3d([dict(boxes_3d=b, scores_3d=s, labels_3d=l) for b, s, l in passes], metas, cfg)]
+        return [merge_aug_bboxes_3d_device(boxes, scores.float(), labels, pass_idx, metas, cfg, len(head.class_names))]
 
     def multi_stage_refine_graph(self, obj_centers, obj_coors, obj_result, points, point_infos, pts_feat, batch_idx, mask_data,
                                  mask_anno, img_metas, res_query_feat):

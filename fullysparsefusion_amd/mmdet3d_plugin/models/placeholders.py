@@ -28,7 +28,7 @@ for _reg, _where, _module, _names in (
         (BBOX_ASSIGNERS, "core/bbox/assigners", False, "HybridAssigner FrustumAssigner PointInBoxAssigner DistAssigner MaxIoUAssigner"),
         (PIPELINES, "datasets/pipelines (training augmentations)", False,
          "MyLoadPointsFromMultiSweeps LoadAnnotations3D ObjectSample ObjectRangeFilter ObjectNameFilter PointShuffle MyObjectSample "
-         "MyObjectRangeFilter MyGlobalRotScaleTrans MyRandomFlip3D MyPointShuffle"),
+         "MyObjectRangeFilter MyRandomFlip3D MyPointShuffle"),
         (DATASETS, "datasets", False, "NuScenesDataset CBGSDataset Argo2Dataset My_Resample_Dataset RepeatDataset"),
         (HOOKS, "core/hook/fsd_hooks.py", False, "DisableAugmentationHook EnableFSDDetectionHook EnableFSDDetectionHookIter")):
     for _n in _names.split():

@@ -31,7 +31,7 @@ extern "C" {
 const char* fsf_status_string(int status);
 /* ABI version, bumped whenever a signature changes or an entry point is added; a loader compares fsf_abi_version() of the
  * library it found with the FSF_ABI_VERSION of the header it was written against. */
-#define FSF_ABI_VERSION 21
+#define FSF_ABI_VERSION 22
 int fsf_abi_version(void);
 
 /* Process-wide algorithm switches (A/B runs and tests that compare two device paths in one process); the defaults are the
@@ -393,6 +393,40 @@ int fsf_assemble_sweeps(const float* raw, int64_t n_rows, int32_t load_dim, cons
                         const double* sweep_params, const uint8_t* sweep_transform, const uint8_t* sweep_remove_close,
                         float close_radius, const float* pc_range, int32_t norm_col, float norm_mean, float norm_std, float* out,
                         int64_t* count_dev, int64_t* count_host, void* workspace, int64_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * K33  test-time augmentation (flip / rotation / scale TTA; docs/kernels/K33_test_time_aug.md)
+ * K33a fsf_augment_points replaces, per augmentation, the host passes GlobalRotScaleTrans / MyGlobalRotScaleTrans (preset
+ *   pcd_rot_factor / pcd_scale_factor, translation std 0: projects/mmdet3d_plugin/datasets/pipelines/transforms_3d.py:15-180),
+ *   RandomFlip3D (preset pcd_horizontal_flip / pcd_vertical_flip) and PointsRangeFilter inside MyMultiScaleFlipAug3D
+ *   (projects/mmdet3d_plugin/datasets/pipelines/test_time_aug.py:78-113), for A augmentations of ONE uploaded cloud.
+ *   points    f32 [n_rows, cols] device (cols >= 3; columns 0..2 = xyz, the rest are copied unchanged)
+ *   aug_desc  f32 [num_augs, 7] HOST: (cos, sin, scale, angle, rotate, flip_h, flip_v) — cos / sin of the fp32 angle as the host
+ *             computes them, rotate = 0 for an angle of exactly zero (not evaluated); num_augs <= fsf_augment_max() = 32
+ *   pc_range  f32 [6] HOST or NULL: the strict in-range test, on the AUGMENTED xyz
+ *   out       f32 [num_augs * n_rows, cols] (capacity): augmentation k's surviving rows, in source order, at rows
+ *             offsets[k] .. offsets[k + 1]
+ *   offsets   i64 [num_augs + 1] device (and on the host too when offsets_host != NULL: one stream sync)
+ * Per row: x' = x c - y s, y' = x s + y c (two rounded products and one rounded sum each, no FMA), then x, y, z times scale,
+ * then y -> -y (horizontal), then x -> -x (vertical).  Bit-identical to the host classes.
+ * K33b fsf_aug_boxes_map_back: mmdet3d's bbox3d_mapping_back [UNVENDORED mmdet3d.core.bbox.transforms] for the concatenated
+ *   per-pass results of merge_aug_bboxes_3d [UNVENDORED mmdet3d.core.post_processing.merge_augs], plus the rotation the
+ *   reference's TTA adds: undo vertical flip, horizontal flip, scale, rotation.
+ *   boxes     f32 [m, box_dim] with row stride box_stride (box_dim 7 | 9: x y z w l h yaw [vx vy]); scores f32 [m];
+ *   labels    i64 [m] (class index; outside [0, num_classes) drops the box); pass_idx i32 [m] (the row's augmentation)
+ *   pass_desc f32 [num_passes, 7] HOST: as aug_desc, with scale = fp32(1 / s)
+ *   boxes_out f32 [m, box_dim]; boxes_nms f32 [m, 5] = xywhr2xyxyr(bev); scores_t f32 [num_classes, m] (the box's score in its
+ *   label's row, -inf elsewhere): the inputs of fsf_class_rank_desc, fsf_nms_bev_multiclass_capped and fsf_nms_select.
+ * Nothing here synchronises except fsf_augment_points with offsets_host.
+ */
+int32_t fsf_augment_max(void);
+int64_t fsf_augment_points_workspace_bytes(int64_t n_rows, int32_t num_augs);
+int fsf_augment_points(const float* points, int64_t n_rows, int32_t cols, const float* aug_desc, int32_t num_augs,
+                       const float* pc_range, float* out, int64_t* offsets_dev, int64_t* offsets_host, void* workspace,
+                       int64_t workspace_bytes, void* stream);
+int fsf_aug_boxes_map_back(const float* boxes, int64_t box_stride, int32_t box_dim, const float* scores, const int64_t* labels,
+                           const int32_t* pass_idx, int64_t m, const float* pass_desc, int32_t num_passes, int32_t num_classes,
+                           float* boxes_out, float* boxes_nms, float* scores_t, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * K13-K15  LiDAR -> camera projection + per-point instance-mask gather
