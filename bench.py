@@ -9,6 +9,7 @@ process per GPU.
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
     python bench.py --steps K --dump-outputs DIR     # + the last timed step's outputs as DIR/<name>.npy (rank 0)
+    python bench.py --full                            # + every measurement beside the headline (below)
 
 A "step" is one full forward of the detector (FSF.simple_test: voxelize -> DynamicScatterVFE -> SimpleSparseUNet ->
 neck -> projection + mask gather + image fusion + seg head -> camera-query grouping + SIR -> LiDAR-query pre-voxelize,
@@ -19,12 +20,19 @@ caches saw last.  `--hot-path-only` stops after the three query-generation stage
 loss + gradient all-reduce + AdamW instead.  Frames are independent, so for inference N ranks are N replicas with no
 data-path collective (weak scaling); the only collectives are the barrier and the max-over-ranks of the timed region.
 
-Rank 0 prints ONE JSON line.  Besides the contract's fields it carries
+Rank 0 prints ONE JSON line.  A plain run does only what that line's headline needs: set-up, warm-up, the timed steps, the dump
+and the line (the contract's fields, the workload's description and the query / box counts the timed output carries).  With
+`--full` it then measures, outside the timed region, and adds to the line
+  * `frame_front`: the same loop with nothing announced, and the announced loop once more behind it;
+  * `launches`: C-ABI calls, ATen device ops and host waits of one extra untimed frame; `stages`: the query-generation stages alone;
+  * `h2d`, `trained_like`, `train`: the host-buffer loop, the trained-like variant and a short training step, beside the headline;
   * `roofline`: the dominant kernel (sparse-conv forward) timed with HIP events in an instrumented pass over the same
     frames, fp32-equivalent flops against the ceiling of the matrix pipe the kernel actually issues on, plus the contract's
     fp32-pipe peak, per-kernel split, `hbm` = GB/s and fraction of 8 TB/s of the scatter / gather / segmented-reduce /
     projection / fused-linear kernels (algorithmic bytes of SURVEY.md section 8d / HIP-event time), and `frame_roofline_ms`;
-  * `cpu_baseline`: the CPU oracle (kind "port") on ONE FULL 10-sweep frame through stages 1-3, per-stage times.
+  * `cpu_baseline`: the CPU oracle (kind "port") on ONE FULL 10-sweep frame through stages 1-3, per-stage times;
+  * for `--train`, `roofline` of the weight-gradient kernel and `allreduce` (exposed vs isolated collective time) instead.
+The `--no-*` switches trim a `--full` run.
 """
 import argparse
 import copy
@@ -57,11 +65,14 @@ def parse():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--sweeps", type=int, default=10, help="10 = BASELINE config 3 input; 1 = config 2 (parity case)")
     ap.add_argument("--frames", type=int, default=4, help="distinct synthetic frames the timed loop rotates over")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure everything beside the headline (module docstring); a plain run "
+                         "stops at the result line")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU oracle baseline")
+    ap.add_argument("--no-roofline", action="store_true", help="--full without the launch counts, roofline pass and stage split")
     ap.add_argument("--no-describe", action="store_true",
-                    help="skip the extra untimed stages-1-3 pass that counts the queries (profiling runs: the per-frame "
-                         "kernel table then holds exactly warmup + steps forwards)")
+                    help="no query / box counts in the line; with --full, no extra untimed stages-1-3 pass that counts the "
+                         "queries (profiling runs: the per-frame kernel table then holds exactly warmup + steps forwards)")
     ap.add_argument("--train", action="store_true",
                     help="time the training step instead (BASELINE configs 3/4): fwd + bwd of a dummy scalar loss over the "
                          "hot-path outputs + bucketed gradient all-reduce over RCCL + AdamW")
@@ -73,8 +84,8 @@ def parse():
                     help="time the trained-like variant INSTEAD of the headline workload: 40 small 2-D instances per frame and "
                          "segmentation / classification biases calibrated so that ~5 %% of the points are foreground and a few hundred "
                          "boxes reach the NMS (what FSF_nuScenes_config.py:22-30,377-384 thresholds leave with trained weights); "
-                         "the default run reports it BESIDE the headline (`trained_like`)")
-    ap.add_argument("--no-trained-like", action="store_true", help="skip the trained-like side measurement of the default run")
+                         "a --full run reports it BESIDE the headline (`trained_like`)")
+    ap.add_argument("--no-trained-like", action="store_true", help="skip the trained-like side measurement of a --full run")
     ap.add_argument("--serial", action="store_true",
                     help="profiling runs: the two query branches back to back on one stream, the U-Net's lateral / plan streams off — every "
                          "kernel then runs alone on the device, so a rocprofv3 trace of this setting holds IN-SITU kernel durations "
@@ -82,8 +93,8 @@ def parse():
     ap.add_argument("--no-frame-front", action="store_true",
                     help="do not announce the next frame to the detector (FSF.set_next_frame): every frame's front is issued inside "
                          "its own frame, as in rounds 1-5")
-    ap.add_argument("--no-h2d", action="store_true", help="skip the host-buffer (PCIe-inclusive) side measurement of the default run")
-    ap.add_argument("--no-train-block", action="store_true", help="skip the short training-step side measurement of the default run")
+    ap.add_argument("--no-h2d", action="store_true", help="skip the host-buffer (PCIe-inclusive) side measurement of a --full run")
+    ap.add_argument("--no-train-block", action="store_true", help="skip the short training-step side measurement of a --full run")
     ap.add_argument("--hot-path-only", action="store_true",
                     help="time stages 1-3 only (segmentor + fusion, camera queries, LiDAR queries), no heads / refine / NMS")
     ap.add_argument("--dump-outputs", metavar="DIR",
@@ -320,12 +331,15 @@ def count_launch_sources(model, inp, hot_path_only=False):
 
 
 def describe_output(model, inp, out, args):
-    """Query / box counts of the timed workload (one extra untimed pass when the timed output does not carry them)."""
+    """Query / box counts of the timed workload.  The full forward's output carries only the boxes: its query counts take one extra
+    untimed pass, which only a `--full` run spends."""
     if args.no_describe:
         return {}
     if not (args.train or args.hot_path_only):
-        hot = step(model, inp, hot_path_only=True)
         extra = {"boxes_out": int(sum(len(r["boxes_3d"]) for r in out))}
+        if not args.full:
+            return extra
+        hot = step(model, inp, hot_path_only=True)
     else:
         hot, extra = out, {}
     return dict(camera_queries=int(hot["frustum_obj_feats"].shape[0]), lidar_queries=int(hot["fsd_obj_feats"].shape[0]), **extra)
@@ -1134,7 +1148,7 @@ def main():
                     m.test_cfg["concurrent_query_branches"] = False
                 except TypeError:
                     pass
-    model_cpu = (None if args.no_cpu_baseline or rank != 0 or world != 1 or args.train or args.dataset != "nuscenes"
+    model_cpu = (None if not args.full or args.no_cpu_baseline or rank != 0 or world != 1 or args.train or args.dataset != "nuscenes"
                  else copy.deepcopy(model).cpu())
     nframes = max(1, args.frames)
     pool = [make_inputs(args.sweeps, seed=rank * 131 + j, device=device, frames=args.frames_per_gpu, dataset=args.dataset,
@@ -1228,8 +1242,9 @@ def main():
             result["metric"] += " (trained-like variant: calibrated foreground / candidate counts, 40 masks per frame)"
         if dumped is not None:
             result["dump_outputs"] = dump_outputs(*dumped, args.dump_outputs)
+    # everything below measures beside the headline, outside the timed region: `--full` only
     ms_plain = None
-    if not args.train:  # (all ranks, outside the timed region) the same loop WITHOUT announcing the next frame: rounds 1-5's loop
+    if args.full and not args.train:  # (all ranks) the same loop WITHOUT announcing the next frame: rounds 1-5's loop
         ms_plain = result["ms_per_step"] if rank == 0 else None
         if not args.no_frame_front:
             torch.cuda.synchronize()
@@ -1257,11 +1272,11 @@ def main():
                         "announced (`--no-frame-front` times that loop as the headline), `ms_per_step_announced_repeat` = the announced "
                         "loop again behind it (the loops of a process get faster as it warms: compare these two, not the headline, with "
                         "the unannounced figure; interleaved rounds: tools/profiling/frame_front_ab.py, profiles/r6_frame_front_ab.txt)"}
-    if args.train and not args.no_roofline:  # (all ranks: the measurement runs real collectives)
+    if args.full and args.train and not args.no_roofline:  # (all ranks: the measurement runs real collectives)
         roof, allreduce = train_extras(train_step, pool, args.steps, world, dist, device)
         if rank == 0:
             result["roofline"], result["allreduce"] = roof, allreduce
-    if rank == 0 and not args.no_roofline and not args.train:
+    if args.full and rank == 0 and not args.no_roofline and not args.train:
         result["launches"] = count_launch_sources(model, last, args.hot_path_only)
         n = min(args.steps, 2 * nframes)
         conv_t, hbm_t = instrumented_pass(model, pool, n, args.hot_path_only)
@@ -1275,7 +1290,7 @@ def main():
             torch.cuda.synchronize()
             result["stages"] = {"query_generation_ms": round((time.perf_counter() - t0) / n * 1e3, 3),
                                 "full_forward_ms": result["ms_per_step"]}
-    if (rank == 0 and world == 1 and not (args.train or args.hot_path_only or args.trained_like or args.no_h2d)
+    if (args.full and rank == 0 and world == 1 and not (args.train or args.hot_path_only or args.trained_like or args.no_h2d)
             and args.dataset == "nuscenes" and args.frames_per_gpu == 1):
         # BESIDE the headline: the same forward with every frame handed over as host buffers (PCIe-inclusive rate)
         result["h2d"] = h2d_inclusive(model, args.sweeps, [rank * 131 + j for j in range(nframes)], device, args.steps, args.warmup,
@@ -1283,7 +1298,7 @@ def main():
         # (the host-buffer loop announces nothing: with the next frame announced it ran 13.45 ms against 13.11 unannounced on the same
         # box — the upload of frame i + 2, issued when frame i ends, then runs beside frame i + 1's front instead of beside its tail;
         # cause not established further.  Compared with the unannounced resident loop of the same run.)
-    if (rank == 0 and world == 1 and not (args.train or args.hot_path_only or args.trained_like or args.no_trained_like)
+    if (args.full and rank == 0 and world == 1 and not (args.train or args.hot_path_only or args.trained_like or args.no_trained_like)
             and args.dataset == "nuscenes" and args.frames_per_gpu == 1):
         # BESIDE the headline: the same forward on the trained-like variant (see calibrate_trained_like)
         m2 = build_model(device, args.dataset)  # (same seed -> the same random-init weights; the timed model stays untouched)
@@ -1307,10 +1322,10 @@ def main():
             camera_queries=int(hot2["frustum_obj_feats"].shape[0]), lidar_queries=int(hot2["fsd_obj_feats"].shape[0]),
             boxes_out=int(sum(len(r["boxes_3d"]) for r in out2)), **info)
         del m2, pool2
-    if (rank == 0 and world == 1 and not (args.train or args.hot_path_only or args.trained_like or args.no_train_block or args.serial)
+    if (args.full and rank == 0 and world == 1 and not (args.train or args.hot_path_only or args.trained_like or args.no_train_block or args.serial)
             and args.dataset == "nuscenes" and args.frames_per_gpu == 1):
         # BESIDE the headline: BASELINE config 3 is "fwd+bwd" — the training step (`bench.py --train` times it as its own line) for a
-        # few steps, so that the driver's default run sees it too
+        # few steps, so that the forward's --full line carries it too
         torch.cuda.empty_cache()
         m3 = build_model(device, args.dataset)
         ts = TrainStep(m3)

@@ -4,11 +4,11 @@ tag=$1
 out=gpurun_out/final_$tag
 mkdir -p $out
 export TMPDIR=/tmp
-python bench.py > $out/bench.json 2> $out/bench.err
-python bench.py --train --steps 10 --warmup 3 > $out/bench_train.json 2>> $out/bench.err
-python bench.py --train --frames-per-gpu 2 --steps 6 --warmup 2 > $out/bench_train_bs2.json 2>> $out/bench.err
-python bench.py --dataset av2 --no-cpu-baseline > $out/bench_av2.json 2>> $out/bench.err
-python bench.py --trained-like --no-cpu-baseline > $out/bench_trained_like.json 2>> $out/bench.err
+python bench.py --full > $out/bench.json 2> $out/bench.err
+python bench.py --full --train --steps 10 --warmup 3 > $out/bench_train.json 2>> $out/bench.err
+python bench.py --full --train --frames-per-gpu 2 --steps 6 --warmup 2 > $out/bench_train_bs2.json 2>> $out/bench.err
+python bench.py --full --dataset av2 --no-cpu-baseline > $out/bench_av2.json 2>> $out/bench.err
+python bench.py --full --trained-like --no-cpu-baseline > $out/bench_trained_like.json 2>> $out/bench.err
 bash tools/profiling/run_prof.sh fwd_$tag > /dev/null 2>&1
 cp gpurun_out/fwd_${tag}_kernels.txt $out/kernel_stats_full_forward.txt
 cp gpurun_out/fwd_${tag}_bench.json $out/bench_under_rocprof.json

@@ -23,12 +23,12 @@ prof train_step 7 --train --no-roofline --steps 5 --warmup 2
 # files are committed as profiles/r4_* afterwards)
 cp $out/kernel_stats_full_forward_serial.txt profiles/r4_kernel_stats_full_forward_serial.txt
 cp $out/kernel_stats_full_forward.txt profiles/r4_kernel_stats_full_forward.txt
-python bench.py > $out/bench_final.json 2>> $out/bench.err
-python bench.py --sweeps 1 --no-cpu-baseline --no-train-block > $out/bench_config2_1sweep.json 2>> $out/bench.err
-python bench.py --train --steps 10 --warmup 3 > $out/bench_train.json 2>> $out/bench.err
-python bench.py --train --frames-per-gpu 2 --steps 6 --warmup 2 > $out/bench_train_bs2.json 2>> $out/bench.err
-python bench.py --dataset av2 --no-cpu-baseline > $out/bench_av2.json 2>> $out/bench.err
-python bench.py --trained-like --no-cpu-baseline > $out/bench_trained_like.json 2>> $out/bench.err
+python bench.py --full > $out/bench_final.json 2>> $out/bench.err
+python bench.py --full --sweeps 1 --no-cpu-baseline --no-train-block > $out/bench_config2_1sweep.json 2>> $out/bench.err
+python bench.py --full --train --steps 10 --warmup 3 > $out/bench_train.json 2>> $out/bench.err
+python bench.py --full --train --frames-per-gpu 2 --steps 6 --warmup 2 > $out/bench_train_bs2.json 2>> $out/bench.err
+python bench.py --full --dataset av2 --no-cpu-baseline > $out/bench_av2.json 2>> $out/bench.err
+python bench.py --full --trained-like --no-cpu-baseline > $out/bench_trained_like.json 2>> $out/bench.err
 bash tools/profiling/pmc_traffic.sh r4 > /dev/null 2>&1
 cp gpurun_out/r4_pmc_traffic.json $out/pmc_traffic.json
 { hdr; echo "# K21 / K22 / K22s / segmented max at the LiDAR-query SIR stack's shapes: round-3 end state (ab_prev) vs this commit, same box, twice"

@@ -26,14 +26,14 @@ cp $out/kernel_stats_full_forward.txt profiles/r5_kernel_stats_full_forward.txt
 bash tools/profiling/pmc_traffic.sh r5 > /dev/null 2>&1
 cp gpurun_out/r5_pmc_traffic.json $out/pmc_traffic.json
 cp gpurun_out/r5_pmc_traffic.json profiles/r5_pmc_traffic.json
-python bench.py > $out/bench_final.json 2>> $out/bench.err
-python bench.py --sweeps 1 --no-cpu-baseline --no-train-block > $out/bench_config2_1sweep.json 2>> $out/bench.err
-python bench.py --train --steps 10 --warmup 3 > $out/bench_train.json 2>> $out/bench.err
+python bench.py --full > $out/bench_final.json 2>> $out/bench.err
+python bench.py --full --sweeps 1 --no-cpu-baseline --no-train-block > $out/bench_config2_1sweep.json 2>> $out/bench.err
+python bench.py --full --train --steps 10 --warmup 3 > $out/bench_train.json 2>> $out/bench.err
 python bench.py --train --hot-path-only --steps 10 --warmup 3 --no-roofline > $out/bench_train_query_stages_only.json 2>> $out/bench.err
-python bench.py --train --frames-per-gpu 2 --steps 6 --warmup 2 > $out/bench_train_bs2.json 2>> $out/bench.err
-python bench.py --train --dataset av2 --steps 10 --warmup 3 > $out/bench_train_av2.json 2>> $out/bench.err
-python bench.py --dataset av2 --no-cpu-baseline > $out/bench_av2.json 2>> $out/bench.err
-python bench.py --trained-like --no-cpu-baseline > $out/bench_trained_like.json 2>> $out/bench.err
+python bench.py --full --train --frames-per-gpu 2 --steps 6 --warmup 2 > $out/bench_train_bs2.json 2>> $out/bench.err
+python bench.py --full --train --dataset av2 --steps 10 --warmup 3 > $out/bench_train_av2.json 2>> $out/bench.err
+python bench.py --full --dataset av2 --no-cpu-baseline > $out/bench_av2.json 2>> $out/bench.err
+python bench.py --full --trained-like --no-cpu-baseline > $out/bench_trained_like.json 2>> $out/bench.err
 { hdr; python tools/profiling/planes_layers.py 2>/dev/null; } > $out/spconv_layers_k9b_vs_k9d.txt
 { hdr; python tools/profiling/k22_calls.py 2>/dev/null; } > $out/k22_family_calls.txt
 { hdr; python tools/profiling/sync_sites.py 2>/dev/null; } > $out/host_sync_sites.txt
