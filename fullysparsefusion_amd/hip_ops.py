@@ -23,6 +23,8 @@ _ARGTYPES = {
     "fsf_augment_points_workspace_bytes": [c_i64, c_i32],
     "fsf_augment_points": [_P, c_i64, c_i32, _P, c_i32, _P, _P, _P, _P, _P, c_i64, _P],
     "fsf_aug_boxes_map_back": [_P, c_i64, c_i32, _P, _P, _P, c_i64, _P, c_i32, c_i32, _P, _P, _P, _P],
+    "fsf_mask_extents": [_P, c_i64, c_i32, c_i32, _P, c_i64, _P, c_i64, _P],
+    "fsf_paint_instance_masks": [_P, _P, c_i64, _P, _P, _P, c_i32, _P, _P, c_i32, c_i32, c_i32, _P, _P],
     "fsf_voxelize_dynamic": [_P, c_i64, c_i32, c_i32, _P, _P, _P, _P, _P, _P],
     "fsf_vfe_decorate": [_P, c_i64, c_i32, c_i32, _P, c_i32, _P, _P, _P, _P, c_i32, c_i32, _P, c_i32, _P],
     "fsf_vote_centers_keys": [_P, c_i32, _P, c_i32, _P, c_i32, _P, _P, _P, c_i64, c_i32, c_i32, _P, _P, _P, c_i32, _P, _P, _P, _P],
@@ -251,6 +253,58 @@ def aug_boxes_map_back(boxes: torch.Tensor, scores: torch.Tensor, labels: torch.
                                       desc, p, int(num_classes), ptr(out), ptr(nms), ptr(scores_t), stream_ptr()),
           "fsf_aug_boxes_map_back")
     return out, nms, scores_t
+
+
+def mask_extents(masks: torch.Tensor, mask_index: torch.Tensor = None, out: torch.Tensor = None):
+    """fsf_mask_extents (K34a): full-resolution masks u8 / bool [N, H, W] on the device -> i32 [n_out, 4] (y0, x0, h, w) of each
+    mask's nonzero pixels ((0, 0, 0, 0) when empty).  `mask_index` i32 [n_out] (device) picks and orders the masks measured (default:
+    all N).  `out` may be a caller-owned i32 view with row stride >= 4 (e.g. rows of a larger table).  One read of each mask; no sync."""
+    require_cuda(masks, mask_index, out)
+    assert masks.dim() == 3 and masks.dtype in (torch.uint8, torch.bool), "masks must be u8 / bool [N, H, W]"
+    masks = masks.contiguous()
+    n, h, w = masks.shape
+    if mask_index is not None:
+        assert mask_index.dtype == torch.int32 and mask_index.dim() == 1
+        mask_index = mask_index.contiguous()
+    n_out = n if mask_index is None else mask_index.numel()
+    if out is None:
+        out = torch.empty((n_out, 4), dtype=torch.int32, device=masks.device)
+    assert out.dtype == torch.int32 and out.dim() == 2 and out.size(0) == n_out and out.size(1) >= 4 and out.stride(1) == 1
+    check(_L().fsf_mask_extents(c_p(masks.data_ptr()) if masks.numel() else c_p(None), n, h, w, ptr(mask_index), n_out,
+                                c_p(out.data_ptr()), out.stride(0), stream_ptr()), "fsf_mask_extents")
+    return out
+
+
+def paint_instance_masks(table: torch.Tensor, src_off: torch.Tensor, plane_ptr: torch.Tensor, plane_src_hw: torch.Tensor,
+                         plane_scale: torch.Tensor, dst_hw, out_dtype=torch.uint8, masks: torch.Tensor = None,
+                         extents: torch.Tensor = None, out: torch.Tensor = None):
+    """fsf_paint_instance_masks (K34b): object table i32 [M, 8] (plane, y0, x0, h, w, pitch, ext_row, id) in paint order, grouped per
+    plane by plane_ptr i32 [P + 1]; src_off i64 [M]; per-plane source size plane_src_hw i32 [P, 2] and f32 scale [P, 2] ->
+    out_dtype (u8 | i32) [P, dst_h, dst_w], every element written once.  `masks`: the u8 buffer src_off indexes (None when every row is
+    a solid rectangle); `extents`: i32 [*, 4] rows that ext_row >= 0 reads.  The caller guarantees every rectangle lies inside its
+    source (mmdet3d_plugin/datasets/mask_paint.py builds and checks the table).  No sync."""
+    require_cuda(table, src_off, plane_ptr, plane_src_hw, plane_scale, masks, extents, out)
+    assert table.dtype == torch.int32 and table.dim() == 2 and table.size(1) == 8
+    assert src_off.dtype == torch.int64 and src_off.numel() == table.size(0)
+    assert plane_ptr.dtype == torch.int32 and plane_src_hw.dtype == torch.int32 and plane_scale.dtype == torch.float32
+    num_planes = plane_ptr.numel() - 1
+    assert num_planes >= 0 and plane_src_hw.numel() == 2 * num_planes and plane_scale.numel() == 2 * num_planes
+    assert out_dtype in (torch.uint8, torch.int32)
+    if masks is not None:
+        assert masks.dtype in (torch.uint8, torch.bool)
+        masks = masks.contiguous()
+    if extents is not None:
+        assert extents.dtype == torch.int32 and extents.dim() == 2 and extents.size(1) == 4
+        extents = extents.contiguous()
+    dh, dw = int(dst_hw[0]), int(dst_hw[1])
+    if out is None:
+        out = torch.empty((num_planes, dh, dw), dtype=out_dtype, device=table.device)
+    assert out.dtype == out_dtype and out.is_contiguous() and out.numel() == num_planes * dh * dw
+    table, src_off = table.contiguous(), src_off.contiguous()
+    check(_L().fsf_paint_instance_masks(ptr(table), ptr(src_off), table.size(0), ptr(plane_ptr.contiguous()), ptr(plane_src_hw.contiguous()),
+                                        ptr(plane_scale.contiguous()), num_planes, ptr(extents), ptr(masks), dh, dw, out.element_size(),
+                                        ptr(out), stream_ptr()), "fsf_paint_instance_masks")
+    return out
 
 
 def voxelize_dynamic(points: torch.Tensor, voxel_size, pc_range, grid, batch_idx: int = 0, want_zyx=True,

@@ -2,3 +2,4 @@ from .pipelines import (Collect3D, DevicePointAssembler, Compose, DefaultFormatB
                         LoadPointsFromFile, LoadPointsFromMultiSweeps, MultiScaleFlipAug3D, MyLoadPointsFromFile,
                         MyLoadPointsFromMultiSweeps, NormalizePoints, PointsRangeFilter, RandomFlip3D, SaveNoAugPoints,
                         frame_to_device)
+from .mask_paint import PaintMasksFromDetections  # noqa: F401,E402

@@ -31,7 +31,7 @@ extern "C" {
 const char* fsf_status_string(int status);
 /* ABI version, bumped whenever a signature changes or an entry point is added; a loader compares fsf_abi_version() of the
  * library it found with the FSF_ABI_VERSION of the header it was written against. */
-#define FSF_ABI_VERSION 22
+#define FSF_ABI_VERSION 23
 int fsf_abi_version(void);
 
 /* Process-wide algorithm switches (A/B runs and tests that compare two device paths in one process); the defaults are the
@@ -427,6 +427,37 @@ int fsf_augment_points(const float* points, int64_t n_rows, int32_t cols, const 
 int fsf_aug_boxes_map_back(const float* boxes, int64_t box_stride, int32_t box_dim, const float* scores, const int64_t* labels,
                            const int32_t* pass_idx, int64_t m, const float* pass_desc, int32_t num_passes, int32_t num_classes,
                            float* boxes_out, float* boxes_nms, float* scores_t, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * K34  camera instance-id planes painted from 2-D detections (docs/kernels/K34_mask_paint.md)
+ * Replaces the offline round trip tools/mask_tools/save_mask_nusc.py / save_mask_argo2.py (paint_obj, paint_obj_bbox_only,
+ *   get_instance_mask: PNG planes + anno.json) -> LoadMaskFromFiles (projects/mmdet3d_plugin/datasets/pipelines/loading.py:22-339).
+ *   Selection, order and ids are host work (mmdet3d_plugin/datasets/mask_paint.py); these two kernels do the pixels.
+ * K34a fsf_mask_extents: the nonzero extent of full-resolution masks.
+ *   masks       u8 / bool [n_masks, h, w], 16-byte aligned, h * w % 16 == 0 (else FSF_ERR_UNSUPPORTED)
+ *   mask_index  i32 [n_out] device (the masks to measure, in output order) or NULL (identity, n_out <= n_masks)
+ *   out         i32 rows of 4 with row stride out_stride (>= 4): (y0, x0, h, w) of mask mask_index[k]'s nonzero pixels,
+ *               (0, 0, 0, 0) for an empty mask.  One workgroup per output row; each mask is read once.
+ * K34b fsf_paint_instance_masks: an ordered object table -> num_planes output planes [num_planes, dst_h, dst_w].
+ *   table       i32 [n_rows, 8] device: (plane, y0, x0, h, w, pitch, ext_row, id).  Rows of one plane are contiguous, in paint
+ *               order: a pixel takes the id of the first row whose mask covers it, 0 where none does.  (y0, x0, h, w) is the
+ *               object's rectangle in SOURCE pixels of its plane; ext_row >= 0 reads it from extents[ext_row] instead (K34a's
+ *               output, so device masks never go through the host).  pitch 0: the whole rectangle is covered (bbox_only);
+ *               else source pixel (y, x) of the object is masks[src_off[row] + y * pitch + x] != 0 (src_off may be "virtual":
+ *               a crop starting at byte c with origin (y0, x0) has src_off = c - y0 * pitch - x0).
+ *   src_off     i64 [n_rows] device; plane_ptr i32 [num_planes + 1] device (CSR over the table rows)
+ *   plane_src_hw i32 [num_planes, 2] device: source size; plane_scale f32 [num_planes, 2] device: (h / dst_h, w / dst_w) rounded to
+ *               f32.  A plane whose source size differs from (dst_h, dst_w) is resized nearest on the fly: source row of output row
+ *               i = min(floor(f32(i) * scale_y), src_h - 1) (LoadMaskFromFiles._resize_nearest), same for columns.
+ *   out         u8 (out_elem_bytes 1; ids above 255 keep their low byte: the caller checks) or i32 (4) [num_planes, dst_h, dst_w],
+ *               16-byte aligned, dst_w % 16 == 0.  Every element is written exactly once (no memset needed).
+ * The caller guarantees every rectangle lies inside its mask's source.  Nothing here synchronises.
+ */
+int fsf_mask_extents(const uint8_t* masks, int64_t n_masks, int32_t h, int32_t w, const int32_t* mask_index, int64_t n_out,
+                     int32_t* out, int64_t out_stride, void* stream);
+int fsf_paint_instance_masks(const int32_t* table, const int64_t* src_off, int64_t n_rows, const int32_t* plane_ptr,
+                             const int32_t* plane_src_hw, const float* plane_scale, int32_t num_planes, const int32_t* extents,
+                             const uint8_t* masks, int32_t dst_h, int32_t dst_w, int32_t out_elem_bytes, void* out, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * K13-K15  LiDAR -> camera projection + per-point instance-mask gather
