@@ -71,6 +71,7 @@ def lib():
                     "fsf_linear_prepared_weight_bytes", "fsf_linear_prepared_weight_sliced_bytes", "fsf_spconv_split_weight_bytes", "fsf_spconv_split_workspace_bytes",
                     "fsf_planes_bytes", "fsf_planes_scale_count", "fsf_spconv_planes_weight_bytes", "fsf_assemble_sweeps_workspace_bytes",
                     "fsf_augment_points_workspace_bytes",
+                    "fsf_seg_targets_workspace_bytes", "fsf_seg_loss_workspace_bytes",
                     "fsf_get_option", "fsf_order_by_neighbor_mask_workspace_bytes",
                     "fsf_class_rank_desc_workspace_bytes", "fsf_nms_select_capacity", "fsf_cluster_key_survival_workspace_bytes",
                     "fsf_overlap_plan_workspace_bytes", "fsf_group_pairs_workspace_bytes",

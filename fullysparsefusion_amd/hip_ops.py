@@ -25,6 +25,11 @@ _ARGTYPES = {
     "fsf_aug_boxes_map_back": [_P, c_i64, c_i32, _P, _P, _P, c_i64, _P, c_i32, c_i32, _P, _P, _P, _P],
     "fsf_mask_extents": [_P, c_i64, c_i32, c_i32, _P, c_i64, _P, c_i64, _P],
     "fsf_paint_instance_masks": [_P, _P, c_i64, _P, _P, _P, c_i32, _P, _P, c_i32, c_i32, c_i32, _P, _P],
+    "fsf_seg_targets_workspace_bytes": [c_i64, c_i64],
+    "fsf_seg_targets": [_P, c_i64, c_i64, _P, c_i32, _P, c_i32, _P, c_i64, c_i64, _P, c_i32, _P, c_i64, _P, _P, _P, _P, _P],
+    "fsf_seg_loss_workspace_bytes": [c_i64],
+    "fsf_seg_loss_forward": [_P, c_i64, _P, c_i64, c_i64, c_i32, _P, _P, _P, _P, c_f32, c_f32, _P, c_i64, _P, _P, _P, _P],
+    "fsf_seg_loss_backward": [_P, c_i64, _P, c_i64, c_i64, c_i32, _P, _P, _P, _P, c_f32, c_f32, _P, _P, _P, _P, _P, _P],
     "fsf_voxelize_dynamic": [_P, c_i64, c_i32, c_i32, _P, _P, _P, _P, _P, _P],
     "fsf_vfe_decorate": [_P, c_i64, c_i32, c_i32, _P, c_i32, _P, _P, _P, _P, c_i32, c_i32, _P, c_i32, _P],
     "fsf_vote_centers_keys": [_P, c_i32, _P, c_i32, _P, c_i32, _P, _P, _P, c_i64, c_i32, c_i32, _P, _P, _P, c_i32, _P, _P, _P, _P],
@@ -305,6 +310,87 @@ def paint_instance_masks(table: torch.Tensor, src_off: torch.Tensor, plane_ptr: 
                                         ptr(plane_scale.contiguous()), num_planes, ptr(extents), ptr(masks), dh, dw, out.element_size(),
                                         ptr(out), stream_ptr()), "fsf_paint_instance_masks")
     return out
+
+
+def seg_targets(points: torch.Tensor, batch_idx: torch.Tensor, box_ptr: torch.Tensor, boxes: torch.Tensor, box_labels: torch.Tensor,
+                num_classes: int):
+    """fsf_seg_targets (K35a): points f32 [n, >=3] (row stride >= 3), batch_idx i32 / i64 [n], per-sample CSR box_ptr i32 [B + 1],
+    boxes f32 [M, >=7] (x, y, z_bottom, w, l, h, yaw, ...), box_labels i32 [M] (rows < 0 skipped) -> (labels i64 [n],
+    targets f32 [n, 3], mask bool [n], count i32 [1]), all on the device.  The first box of the point's sample that contains it wins.
+    No sync."""
+    require_cuda(points, batch_idx, box_ptr, boxes, box_labels)
+    assert points.dtype == torch.float32 and points.dim() == 2 and points.size(1) >= 3 and points.stride(1) == 1
+    assert batch_idx.dtype in (torch.int32, torch.int64) and batch_idx.dim() == 1 and batch_idx.numel() == points.size(0)
+    assert box_ptr.dtype == torch.int32 and box_ptr.dim() == 1 and box_ptr.numel() >= 1
+    assert boxes.dtype == torch.float32 and boxes.dim() == 2 and boxes.size(1) >= 7 and boxes.stride(1) == 1
+    assert box_labels.dtype == torch.int32 and box_labels.dim() == 1 and box_labels.numel() == boxes.size(0)
+    n, m, dev = points.size(0), boxes.size(0), points.device
+    batch_idx, box_ptr, box_labels = batch_idx.contiguous(), box_ptr.contiguous(), box_labels.contiguous()
+    labels = torch.empty((n,), dtype=torch.int64, device=dev)
+    targets = torch.empty((n, 3), dtype=torch.float32, device=dev)
+    mask = torch.empty((n,), dtype=torch.bool, device=dev)
+    count = torch.empty((1,), dtype=torch.int32, device=dev)
+    h = _L()
+    ws_bytes = h.fsf_seg_targets_workspace_bytes(m, n)
+    ws = _lib.workspace(ws_bytes, dev)
+    pts = c_p(points.data_ptr()) if n else c_p(None)
+    bx = c_p(boxes.data_ptr()) if m else c_p(None)
+    check(h.fsf_seg_targets(pts, n, points.stride(0) if n else 3, ptr(batch_idx), batch_idx.element_size(), ptr(box_ptr),
+                            box_ptr.numel() - 1, bx, m, boxes.stride(0) if m else 7, ptr(box_labels), int(num_classes), ptr(ws),
+                            ws.numel(), ptr(labels), ptr(targets), ptr(mask), ptr(count), stream_ptr()), "fsf_seg_targets")
+    return labels, targets, mask, count
+
+
+def _seg_loss_operands(logits, votes, labels, targets, mask, class_weight):
+    require_cuda(logits, votes, labels, targets, mask, class_weight)
+    assert logits.dtype == torch.float32 and logits.dim() == 2 and logits.stride(1) == 1
+    n, c = logits.shape
+    assert votes.dtype == torch.float32 and votes.dim() == 2 and votes.shape == (n, 3 * c) and votes.stride(1) == 1
+    assert labels.dtype == torch.int64 and labels.dim() == 1 and labels.numel() == n
+    assert targets.dtype == torch.float32 and targets.shape == (n, 3)
+    assert mask.dtype in (torch.bool, torch.uint8) and mask.dim() == 1 and mask.numel() == n
+    assert class_weight.dtype == torch.float32 and class_weight.numel() == c
+    ld_l = logits.stride(0) if n > 1 else c
+    ld_v = votes.stride(0) if n > 1 else 3 * c
+    return (n, c, ld_l, ld_v, labels.contiguous(), targets.contiguous(), mask.contiguous().view(torch.uint8), class_weight.contiguous())
+
+
+def seg_loss_forward(logits: torch.Tensor, votes: torch.Tensor, labels: torch.Tensor, targets: torch.Tensor, mask: torch.Tensor,
+                     class_weight: torch.Tensor, ce_weight: float, vote_weight: float):
+    """fsf_seg_loss_forward (K35b): logits f32 [n, C] and votes f32 [n, 3C] (each with its own row stride: column views of one
+    buffer are fine), labels i64 [n], targets f32 [n, 3], mask bool [n], class_weight f32 [C] -> (loss_ce f32 [], loss_vote f32 [],
+    counts i64 [2] = (n, n_valid)).  Weighted CE mean over n and L1 mean over 3 * n_valid (0 when n_valid = 0).  No sync."""
+    n, c, ld_l, ld_v, labels, targets, mask, class_weight = _seg_loss_operands(logits, votes, labels, targets, mask, class_weight)
+    dev = logits.device
+    loss_ce = torch.empty((), dtype=torch.float32, device=dev)
+    loss_vote = torch.empty((), dtype=torch.float32, device=dev)
+    counts = torch.empty((2,), dtype=torch.int64, device=dev)
+    h = _L()
+    ws = _lib.workspace(h.fsf_seg_loss_workspace_bytes(n), dev)
+    check(h.fsf_seg_loss_forward(c_p(logits.data_ptr()) if n else c_p(None), ld_l, c_p(votes.data_ptr()) if n else c_p(None), ld_v, n, c,
+                                 ptr(labels), ptr(targets), ptr(mask), ptr(class_weight), float(ce_weight), float(vote_weight), ptr(ws),
+                                 ws.numel(), ptr(loss_ce), ptr(loss_vote), ptr(counts), stream_ptr()), "fsf_seg_loss_forward")
+    return loss_ce, loss_vote, counts
+
+
+def seg_loss_backward(logits: torch.Tensor, votes: torch.Tensor, labels: torch.Tensor, targets: torch.Tensor, mask: torch.Tensor,
+                      class_weight: torch.Tensor, ce_weight: float, vote_weight: float, counts: torch.Tensor, grad_ce: torch.Tensor,
+                      grad_vote: torch.Tensor):
+    """fsf_seg_loss_backward (K35c): the operands of seg_loss_forward, its `counts` and the upstream gradients of the two losses
+    (f32 scalars on the device) -> dense (grad_logits f32 [n, C], grad_votes f32 [n, 3C]).  The softmax is recomputed.  No sync."""
+    n, c, ld_l, ld_v, labels, targets, mask, class_weight = _seg_loss_operands(logits, votes, labels, targets, mask, class_weight)
+    require_cuda(counts, grad_ce, grad_vote)
+    assert counts.dtype == torch.int64 and counts.numel() == 2
+    assert grad_ce.dtype == torch.float32 and grad_ce.numel() == 1 and grad_vote.dtype == torch.float32 and grad_vote.numel() == 1
+    dev = logits.device
+    grad_logits = torch.empty((n, c), dtype=torch.float32, device=dev)
+    grad_votes = torch.empty((n, 3 * c), dtype=torch.float32, device=dev)
+    if n:
+        check(_L().fsf_seg_loss_backward(c_p(logits.data_ptr()), ld_l, c_p(votes.data_ptr()), ld_v, n, c, ptr(labels), ptr(targets),
+                                         ptr(mask), ptr(class_weight), float(ce_weight), float(vote_weight), ptr(counts.contiguous()),
+                                         ptr(grad_ce.contiguous()), ptr(grad_vote.contiguous()), ptr(grad_logits), ptr(grad_votes),
+                                         stream_ptr()), "fsf_seg_loss_backward")
+    return grad_logits, grad_votes
 
 
 def voxelize_dynamic(points: torch.Tensor, voxel_size, pc_range, grid, batch_idx: int = 0, want_zyx=True,

@@ -1000,13 +1000,17 @@ class FSF(SingleStageFSD):
             stages.append((obj_centers, obj_result, res_query_feat))
         return stages
 
-    def forward_train_graph(self, points, img_metas, mask_data, mask_anno):
+    def forward_train_graph(self, points, img_metas, mask_data, mask_anno, gt_bboxes_3d=None, gt_labels_3d=None):
         """The differentiable graph of `forward_train` (:806-903) — segmentor + image fusion + segmentation head, camera queries
         WITH `frustum_obj_head`, LiDAR queries WITH `bbox_head`, `combine_frustum_and_fsd` (both `combine_*_mlp`), and
         `multi_stage_refine_train` (:905-959: RoI point pooling, `refine_sir_layers`, `lidar_img_mlp`, `position_encoder`,
         `out_proj`, `frustum_refined_head`) — up to the tensors the losses would consume.  Target assignment and the losses themselves
         (`*.loss(...)`: host-side label bookkeeping) are out of scope; the caller supplies a scalar of these
-        outputs (bench.py::dummy_loss: their sum, SURVEY §8(d) config 3)."""
+        outputs (bench.py::dummy_loss: their sum, SURVEY §8(d) config 3).
+
+        With `gt_bboxes_3d` / `gt_labels_3d` (per sample: LiDARInstance3DBoxes or [M, >=7] tensors, and labels) the segmentation
+        head's losses (`segmentor_feat_inhance_train`, :730-770) are added as out["losses"] = dict(loss_sem_seg, loss_vote), on the
+        device with no host wait (K35).  Without them the call and its output are unchanged."""
         self._gather_cache = None
         self._fg_cache = None
         self._img_pre = None
@@ -1018,12 +1022,23 @@ class FSF(SingleStageFSD):
         f_feats, f_centers, f_coors, f_result, f_preds_2d = self.frustum_forward(seg_out_dict, mask_anno, mask_data, point_infos,
                                                                                   img_metas, cluster_center=None)
         l_feats, l_centers, l_coors, l_result = self.fsd_forward(seg_out_dict, img_metas)
+        seg_losses = None
+        if gt_bboxes_3d is not None:
+            # The reference computes the targets on the input points and then keeps the rows of valid_pts_mask; the targets are
+            # per-point functions of xyz and the sample's boxes, so computing them on the kept rows (seg_points, batch_idx), in
+            # whatever order those are, gives the same labels, vote targets and mask for every row.
+            head = self.segmentor.segmentation_head
+            labels, vote_targets, vote_mask = head.get_targets_flat(seg_out_dict["seg_points"], seg_out_dict["batch_idx"],
+                                                                    gt_bboxes_3d, gt_labels_3d)
+            seg_losses = head.losses(seg_out_dict["seg_logits"], seg_out_dict["seg_vote_preds"], labels, vote_targets, vote_mask)
         out = dict(seg=seg_out_dict, frustum_obj_feats=f_feats, frustum_obj_centers=f_centers, frustum_obj_coors=f_coors,
                    frustum_preds_2d=f_preds_2d, frustum_obj_result=f_result, fsd_obj_feats=l_feats, fsd_obj_centers=l_centers,
                    fsd_obj_coors=l_coors, fsd_obj_result=l_result, stage_results=[])
         obj_centers, obj_coors, obj_result, obj_feats, preds_2d = self.combine_frustum_and_fsd(
             f_centers, f_coors, f_result, f_feats, f_preds_2d, l_centers, l_coors, l_result, l_feats)
         out.update(obj_centers=obj_centers, obj_coors=obj_coors, obj_feats=obj_feats, preds_2d=preds_2d)
+        if seg_losses is not None:
+            out["losses"] = seg_losses
         if self.num_extra_stages > 0:
             stages = self.multi_stage_refine_graph(obj_centers, obj_coors, obj_result, seg_out_dict["seg_points"], point_infos,
                                                    seg_out_dict["seg_feats"], seg_out_dict["batch_idx"], mask_data, mask_anno,
@@ -1040,4 +1055,5 @@ class FSF(SingleStageFSD):
         # (this used to run the whole graph and only then raise through `head.loss`)
         raise NotImplementedError(
             "FSF.forward_train: target assignment and the losses (`*.loss(...)`, FSF.py:806-903) are host-side code outside the built "
-            "path; `forward_train_graph(points, img_metas, mask_data, mask_anno)` returns every tensor they would consume")
+            "path; `forward_train_graph(points, img_metas, mask_data, mask_anno)` returns every tensor they would consume, and with "
+            "`gt_bboxes_3d=..., gt_labels_3d=...` also the segmentation head's losses (out['losses'])")

@@ -150,8 +150,25 @@ class VoteSegmentor(nn.Module):
         return dict(seg_points=points, seg_logits=seg_logits, seg_vote_preds=vote_preds, offsets=offsets,
                     seg_feats=feats, batch_idx=pts_coors[:, 0])
 
-    def forward_train(self, *args, **kwargs):
-        raise NotImplementedError("training path (targets + losses) is outside this round's hot path")
+    def forward_train(self, points, img_metas, gt_bboxes_3d, gt_labels_3d, as_subsegmentor=False, extract_feat_only=False):
+        """:276-337.  The targets are computed on the points `extract_feat` returns (with their batch column), not on the input
+        lists: a point's targets depend only on its xyz and its sample's boxes, so this equals the reference's "targets first, then
+        the same rows" whatever order the voxelizer leaves the points in."""
+        head = self.segmentation_head
+        points = self._prep(points)
+        neck_out, pts_coors, points = self.extract_feat(points, img_metas)
+        labels, vote_targets, vote_mask = head.get_targets_flat(points, pts_coors[:, 0], gt_bboxes_3d, gt_labels_3d)
+        if extract_feat_only:
+            return (neck_out, pts_coors, points, labels, vote_targets, vote_mask)
+        feats, valid_pts_mask = neck_out[0], neck_out[1]
+        if not getattr(valid_pts_mask, "fsf_all_true", False):
+            points, pts_coors = points[valid_pts_mask], pts_coors[valid_pts_mask]
+            labels, vote_targets, vote_mask = labels[valid_pts_mask], vote_targets[valid_pts_mask], vote_mask[valid_pts_mask]
+        if as_subsegmentor:
+            losses, preds = head.forward_train(feats, img_metas, labels, vote_targets, vote_mask, return_preds=True)
+            return dict(seg_points=points, seg_logits=preds["seg_logits"], seg_vote_preds=preds["vote_preds"],
+                        offsets=head.decode_vote_targets(preds["vote_preds"]), seg_feats=feats, batch_idx=pts_coors[:, 0], losses=losses)
+        return head.forward_train(feats, img_metas, labels, vote_targets, vote_mask, return_preds=False)
 
 
 @DETECTORS.register_module()

@@ -1,5 +1,5 @@
 """Config `type=` names that are OUT OF SCOPE of the hot path (unused head variants, label
-assigners, losses, dataset classes and hooks) resolve to ONE generic stand-in, so that
+assigners, losses other than models/losses.py's, dataset classes and hooks) resolve to ONE generic stand-in, so that
 `projects/configs/nuScenes/FSF_nuScenes_config.py` loads and the model builds; using one raises, naming what is missing.
 Nothing here computes anything (no silent fallbacks)."""
 import torch.nn as nn
@@ -23,7 +23,7 @@ def out_of_scope(name, where, module=False):
 
 for _reg, _where, _module, _names in (
         (MODELS, "heads / losses of the training path", True,
-         "MultiStageRefineHead GroupCorrectionHead FocalLoss L1Loss SmoothL1Loss CrossEntropyLoss"),
+         "MultiStageRefineHead GroupCorrectionHead FocalLoss SmoothL1Loss"),
         (BBOX_CODERS, "core/bbox/coders", False, "ABSPointBBoxCoder"),
         (BBOX_ASSIGNERS, "core/bbox/assigners", False, "HybridAssigner FrustumAssigner PointInBoxAssigner DistAssigner MaxIoUAssigner"),
         (PIPELINES, "datasets/pipelines (training augmentations)", False,

@@ -124,3 +124,33 @@ def make_frame_av2(seed=0, n_points=150000):
     anno[:, 5] = rng.integers(0, 26, anno.shape[0])
     return dict(points=np.ascontiguousarray(pts), mask_data=mask, mask_anno=anno,
                 lidar2img=make_lidar2img(7, fx=1780.0, cx=1024.0, cy=775.0))
+
+
+def make_gt_boxes(points, num_boxes=40, num_classes=10, seed=0, box_dim=9, num_overlap=4, num_ignored=3, min_range=10.0, max_range=40.0):
+    """Seeded GT for a synthetic frame: (boxes f32 [M, box_dim], labels i64 [M]) in LiDARInstance3DBoxes rows (x, y, z_bottom, w, l,
+    h, yaw[, vx, vy]); box_dim 9 is nuScenes' form, 7 Argoverse 2's.  Each box sits on a point between `min_range` and `max_range` from
+    the sensor, so a few percent of the points fall inside; `num_overlap` extra boxes are shifted copies of earlier
+    ones (overlapping pairs: the first in box order wins), and `num_ignored` rows get label -1 (dropped by the targets)."""
+    assert box_dim in (7, 9)
+    rng = np.random.default_rng(seed + 7000)
+    xyz = np.asarray(points)[:, :3]
+    r = np.hypot(xyz[:, 0], xyz[:, 1])
+    near = np.flatnonzero((r > min_range) & (r < max_range))
+    anchors = xyz[rng.choice(near, num_boxes, replace=False)]
+    w = rng.uniform(0.6, 2.6, num_boxes)
+    l = w * rng.uniform(1.0, 2.5, num_boxes)
+    h = rng.uniform(1.0, 2.6, num_boxes)
+    z = anchors[:, 2] - h * rng.uniform(0.2, 0.8, num_boxes)
+    yaw = rng.uniform(-math.pi, math.pi, num_boxes)
+    rows = np.stack([anchors[:, 0], anchors[:, 1], z, w, l, h, yaw], 1)
+    src = rng.choice(num_boxes, num_overlap, replace=False)
+    shifted = rows[src].copy()
+    shifted[:, 0] += rng.uniform(-0.3, 0.3, num_overlap) * shifted[:, 4]
+    shifted[:, 1] += rng.uniform(-0.3, 0.3, num_overlap) * shifted[:, 3]
+    shifted[:, 6] += rng.uniform(-0.5, 0.5, num_overlap)
+    rows = np.concatenate([rows, shifted], 0)
+    labels = rng.integers(0, num_classes, rows.shape[0])
+    labels[rng.choice(rows.shape[0], num_ignored, replace=False)] = -1
+    if box_dim == 9:
+        rows = np.concatenate([rows, rng.normal(0, 2.0, (rows.shape[0], 2))], 1)
+    return rows.astype(np.float32), labels.astype(np.int64)

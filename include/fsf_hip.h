@@ -460,6 +460,48 @@ int fsf_paint_instance_masks(const int32_t* table, const int64_t* src_off, int64
                              const uint8_t* masks, int32_t dst_h, int32_t dst_w, int32_t out_elem_bytes, void* out, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * K35  segmentation-head targets and losses (docs/kernels/K35_seg_losses.md)
+ * Replaces VoteSegHead.get_targets / get_point_labels / get_vote_target / losses
+ *   (projects/mmdet3d_plugin/models/decode_heads/segmentation_head.py:106-265) with mmdet3d 0.x points_in_boxes_gpu and mmdet 2.14
+ *   CrossEntropyLoss(class_weight) + L1Loss.  Nothing here synchronises; no float atomics (reductions run in a fixed order).
+ * K35a fsf_seg_targets: 3 launches (per-box constants, one lane per point, final count).
+ *   points      f32 rows of pt_stride (>= 3) floats, xyz first; batch_idx i32 (batch_idx_bytes 4) or i64 (8) [n]
+ *   box_ptr     i32 [num_samples + 1] device: CSR of sample b's rows [box_ptr[b], box_ptr[b + 1]) of boxes / box_labels
+ *   boxes       f32 rows of box_stride (>= 7): (x, y, z_bottom, w, l, h, yaw, ...); box_labels i32 [num_boxes] (rows with label < 0 are
+ *               skipped, as if filtered out)
+ *   labels      i64 [n]: label of the FIRST box of the point's sample containing it, num_classes when none
+ *   targets     f32 [n, 3]: sign(d) * sqrt(|d|), d = gravity_center - xyz (0 for background); mask u8 [n]: inside a box
+ *   count       i32 [1] device: number of masked points.  workspace: fsf_seg_targets_workspace_bytes(num_boxes, n)
+ *   Containment (check_pt_in_box3d): cz = f32(z + h / 2); outside when |z - cz| > h / 2; cosa, sina = cos / sin(-yaw) in float64
+ *   rounded once; lx = f32(f32(sx * cosa) + f32(sy * -sina)), ly = f32(f32(sx * sina) + f32(sy * cosa)); inside when
+ *   -l/2 < lx < l/2 and -w/2 < ly < w/2.  Every output element is written once.
+ * K35b fsf_seg_loss_forward: 2 launches.  logits f32 [n, C] (row stride ld_logits), votes f32 [n, 3C] (ld_votes), labels i64 [n] in
+ *   [0, C) (else the CE loss is NaN), targets f32 [n, 3], mask u8 [n], class_weight f32 [C] ->
+ *   loss_ce   = ce_weight * mean_i(w[y_i] * (logsumexp(z_i) - z_i[y_i]))            (divides by n, not by the weight sum)
+ *   loss_vote = vote_weight * mean over masked rows and 3 columns of |v_i[3 y_i + k] - t_ik|, 0 when no row is masked
+ *   counts    i64 [2] = (n, n_valid) for the backward.  fp32 max-subtracted logsumexp per row, fp64 per-workgroup partials, one final
+ *   workgroup.  C <= 256.  workspace: fsf_seg_loss_workspace_bytes(n)
+ * K35c fsf_seg_loss_backward: 1 launch.  grad_ce / grad_vote f32 [1] device (upstream gradients of the two losses) ->
+ *   grad_logits f32 [n, C] dense = (softmax - onehot) * w[y] * ce_weight * grad_ce / n
+ *   grad_votes  f32 [n, 3C] dense = sign(v - t) * vote_weight * grad_vote / (3 n_valid) on the 3 columns of a masked row's class
+ *   (sign(0) = 0), 0 elsewhere and everywhere when n_valid = 0.  The softmax is recomputed.  Every element is written once.
+ */
+int64_t fsf_seg_targets_workspace_bytes(int64_t num_boxes, int64_t n);
+int fsf_seg_targets(const float* points, int64_t n, int64_t pt_stride, const void* batch_idx, int32_t batch_idx_bytes,
+                    const int32_t* box_ptr, int32_t num_samples, const float* boxes, int64_t num_boxes, int64_t box_stride,
+                    const int32_t* box_labels, int32_t num_classes, void* workspace, int64_t workspace_bytes, int64_t* labels,
+                    float* targets, uint8_t* mask, int32_t* count, void* stream);
+int64_t fsf_seg_loss_workspace_bytes(int64_t n);
+int fsf_seg_loss_forward(const float* logits, int64_t ld_logits, const float* votes, int64_t ld_votes, int64_t n, int32_t num_classes,
+                         const int64_t* labels, const float* targets, const uint8_t* mask, const float* class_weight, float ce_weight,
+                         float vote_weight, void* workspace, int64_t workspace_bytes, float* loss_ce, float* loss_vote, int64_t* counts,
+                         void* stream);
+int fsf_seg_loss_backward(const float* logits, int64_t ld_logits, const float* votes, int64_t ld_votes, int64_t n, int32_t num_classes,
+                          const int64_t* labels, const float* targets, const uint8_t* mask, const float* class_weight, float ce_weight,
+                          float vote_weight, const int64_t* counts, const float* grad_ce, const float* grad_vote, float* grad_logits,
+                          float* grad_votes, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * K13-K15  LiDAR -> camera projection + per-point instance-mask gather
  * Replaces: FSF.prj_points_2d (projects/mmdet3d_plugin/models/detectors/FSF.py:169-200) and
  *   FSF.points_in_mask (:202-226) for one batch sample; the caller loops samples like frustum_gather (:228-258).
