@@ -5,6 +5,7 @@ product path raises.  (The CPU oracle under `oracle/` is test infrastructure and
 """
 import ctypes
 import os
+import re
 import threading
 
 import torch
@@ -27,21 +28,55 @@ class FsfHipError(RuntimeError):
     pass
 
 
-def _header_abi_version():
-    """FSF_ABI_VERSION of include/fsf_hip.h (None when the header does not travel with the package)."""
-    import re
+HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "fsf_hip.h")
 
-    path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "fsf_hip.h")
+_ARG_TYPES = {"int": c_i32, "int32_t": c_i32, "int64_t": c_i64, "float": c_f32}
+_RES_TYPES = {"int": c_i32, "int32_t": c_i32, "int64_t": c_i64, "const char*": ctypes.c_char_p}
+
+
+def parse_header(text):
+    """(signatures, defines) of a C header: {name: (argtypes, restype)} for every `fsf_*` function it declares and {name: value}
+    for every integer `#define FSF_*`.  A parameter written with `*` or `[N]` binds as c_void_p; a by-value type other than int /
+    int32_t / int64_t / float, or a return type other than those integers and const char*, raises FsfHipError: nothing is guessed."""
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
+    defines = {k: int(v) for k, v in re.findall(r"^\s*#\s*define\s+(FSF_\w+)\s+\(?(-?\d+)\)?\s*$", text, flags=re.M)}
+    signatures = {}
+    for stmt in re.split(r"[;{}]", re.sub(r"^\s*#.*$", "", text, flags=re.M)):
+        m = re.fullmatch(r"(.*?)\b(fsf_\w+)\s*\((.*)\)", " ".join(stmt.split()))
+        if m is None:
+            continue
+        ret, name, params = re.sub(r" ?\* ?", "*", m.group(1).strip()), m.group(2), m.group(3).strip()
+        if ret not in _RES_TYPES:
+            raise FsfHipError(f"{name}: no ctypes binding for the return type '{ret}'")
+        argtypes = []
+        for p in params.split(",") if params not in ("", "void") else []:
+            if "*" in p or "[" in p:
+                argtypes.append(c_p)
+                continue
+            typ = p.strip().rsplit(" ", 1)[0]  # (the parameter's name dropped)
+            if typ not in _ARG_TYPES:
+                raise FsfHipError(f"{name}: no ctypes binding for the parameter type '{typ}'")
+            argtypes.append(_ARG_TYPES[typ])
+        signatures[name] = (argtypes, _RES_TYPES[ret])
+    return signatures, defines
+
+
+def _read_header():
     try:
-        with open(path) as f:
-            m = re.search(r"#define\s+FSF_ABI_VERSION\s+(\d+)", f.read())
-        return int(m.group(1)) if m else None
-    except OSError:
-        return None
+        with open(HEADER_PATH) as f:
+            return parse_header(f.read())
+    except OSError as e:
+        raise FsfHipError(f"{HEADER_PATH} cannot be read ({e.strerror}): the library's C ABI (signatures, ABI version, constants) "
+                          "is taken from it") from e
+
+
+# every signature and integer constant of include/fsf_hip.h: the header is the one description of the C ABI
+SIGNATURES, DEFINES = _read_header()
 
 
 def lib():
-    """Load (once) and return the ctypes handle.  Fails loudly when the extension has not been built."""
+    """Load (once) and return the ctypes handle, every function the header declares bound to its declared signature.  Fails loudly
+    when the extension has not been built or was built against another ABI version."""
     global _lib
     if _lib is None:
         with _lock:
@@ -52,32 +87,13 @@ def lib():
                         "Run `python -m fullysparsefusion_amd.build` (needs hipcc); there is no CPU fallback."
                     )
                 h = ctypes.CDLL(LIB_PATH)
-                want = _header_abi_version()
-                if want is not None and int(h.fsf_abi_version()) != want:
+                want = DEFINES["FSF_ABI_VERSION"]
+                if int(h.fsf_abi_version()) != want:
                     raise FsfHipError(f"{LIB_PATH} has ABI version {int(h.fsf_abi_version())}, include/fsf_hip.h declares {want}: "
                                       "stale build, run `python -m fullysparsefusion_amd.build`")
-                h.fsf_status_string.restype = ctypes.c_char_p
-                h.fsf_status_string.argtypes = [ctypes.c_int]
-                for name in (
-                    "fsf_unique_rows_workspace_bytes", "fsf_sir_stack_arena_bytes",
-                    "fsf_segment_plan_workspace_bytes",
-                    "fsf_segment_reduce_workspace_bytes",
-                    "fsf_rulebook_workspace_bytes", "fsf_rulebook_to_pairs_workspace_bytes",
-                    "fsf_ingroup_rank_workspace_bytes", "fsf_dynamic_point_pool_workspace_bytes",
-                    "fsf_nms_bev_workspace_bytes", "fsf_nms_bev_multiclass_workspace_bytes", "fsf_nms_bev_multiclass_capped_workspace_bytes",
-                    "fsf_norm_act_backward_workspace_bytes", "fsf_column_stats_workspace_bytes",
-                    "fsf_connected_components_workspace_bytes",
-                    "fsf_spconv_workspace_bytes", "fsf_spconv_backward_weight_workspace_bytes",
-                    "fsf_linear_prepared_weight_bytes", "fsf_linear_prepared_weight_sliced_bytes", "fsf_spconv_split_weight_bytes", "fsf_spconv_split_workspace_bytes",
-                    "fsf_planes_bytes", "fsf_planes_scale_count", "fsf_spconv_planes_weight_bytes", "fsf_assemble_sweeps_workspace_bytes",
-                    "fsf_augment_points_workspace_bytes",
-                    "fsf_seg_targets_workspace_bytes", "fsf_seg_loss_workspace_bytes",
-                    "fsf_get_option", "fsf_order_by_neighbor_mask_workspace_bytes",
-                    "fsf_class_rank_desc_workspace_bytes", "fsf_nms_select_capacity", "fsf_cluster_key_survival_workspace_bytes",
-                    "fsf_overlap_plan_workspace_bytes", "fsf_group_pairs_workspace_bytes",
-                    "fsf_row_planes_bytes", "fsf_linear_prepared_weight_f16_bytes", "fsf_spconv_split_weight_f16_bytes",
-                ):
-                    getattr(h, name).restype = c_i64
+                for name, (argtypes, restype) in SIGNATURES.items():
+                    fn = getattr(h, name)
+                    fn.argtypes, fn.restype = argtypes, restype
                 _lib = h
     return _lib
 

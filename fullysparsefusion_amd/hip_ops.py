@@ -11,167 +11,14 @@ from typing import Optional, Sequence
 import torch
 
 from . import _lib, switches
-from ._lib import FsfHipError, c_f32, c_i32, c_i64, c_p, check, f32_array, i32_array, i64_array, ptr, require_cuda, stream_ptr
+from ._lib import FsfHipError, c_i64, c_p, check, f32_array, i32_array, i64_array, ptr, require_cuda, stream_ptr
 
-ERR_KEY_RANGE = -3  # FSF_ERR_KEY_RANGE (include/fsf_hip.h)
-
-_P = c_p
-_ARGTYPES = {
-    "fsf_assemble_sweeps_workspace_bytes": [c_i64],
-    "fsf_assemble_sweeps": [_P, c_i64, c_i32, _P, c_i32, _P, _P, _P, c_f32, _P, c_i32, c_f32, c_f32, _P, _P, _P, _P, c_i64, _P],
-    "fsf_augment_max": [],
-    "fsf_augment_points_workspace_bytes": [c_i64, c_i32],
-    "fsf_augment_points": [_P, c_i64, c_i32, _P, c_i32, _P, _P, _P, _P, _P, c_i64, _P],
-    "fsf_aug_boxes_map_back": [_P, c_i64, c_i32, _P, _P, _P, c_i64, _P, c_i32, c_i32, _P, _P, _P, _P],
-    "fsf_mask_extents": [_P, c_i64, c_i32, c_i32, _P, c_i64, _P, c_i64, _P],
-    "fsf_paint_instance_masks": [_P, _P, c_i64, _P, _P, _P, c_i32, _P, _P, c_i32, c_i32, c_i32, _P, _P],
-    "fsf_seg_targets_workspace_bytes": [c_i64, c_i64],
-    "fsf_seg_targets": [_P, c_i64, c_i64, _P, c_i32, _P, c_i32, _P, c_i64, c_i64, _P, c_i32, _P, c_i64, _P, _P, _P, _P, _P],
-    "fsf_seg_loss_workspace_bytes": [c_i64],
-    "fsf_seg_loss_forward": [_P, c_i64, _P, c_i64, c_i64, c_i32, _P, _P, _P, _P, c_f32, c_f32, _P, c_i64, _P, _P, _P, _P],
-    "fsf_seg_loss_backward": [_P, c_i64, _P, c_i64, c_i64, c_i32, _P, _P, _P, _P, c_f32, c_f32, _P, _P, _P, _P, _P, _P],
-    "fsf_voxelize_dynamic": [_P, c_i64, c_i32, c_i32, _P, _P, _P, _P, _P, _P],
-    "fsf_vfe_decorate": [_P, c_i64, c_i32, c_i32, _P, c_i32, _P, _P, _P, _P, c_i32, c_i32, _P, c_i32, _P],
-    "fsf_vote_centers_keys": [_P, c_i32, _P, c_i32, _P, c_i32, _P, _P, _P, c_i64, c_i32, c_i32, _P, _P, _P, c_i32, _P, _P, _P, _P],
-    "fsf_voxelize_divfloor": [_P, c_i64, c_i32, _P, _P, c_i32, _P, _P, _P],
-    "fsf_unique_rows_workspace_bytes": [c_i64, c_i32],
-    "fsf_unique_rows": [_P, c_i64, c_i32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, c_i64, _P],
-    "fsf_segment_plan_workspace_bytes": [c_i64, c_i64],
-    "fsf_segment_plan_from_inverse": [_P, c_i64, c_i64, _P, _P, _P, _P, c_i64, _P],
-    "fsf_segment_reduce_workspace_bytes": [c_i64, c_i64, c_i32],
-    "fsf_segment_reduce": [_P, c_i64, c_i64, c_i32, _P, _P, _P, c_i64, c_i32, _P, _P, _P, c_i64, _P],
-    "fsf_segment_reduce_short": [_P, _P, _P, c_i32, c_i64, _P, _P, c_i64, c_i32, _P, _P, _P],
-    "fsf_segment_reduce_backward": [_P, c_i64, c_i32, _P, _P, c_i64, c_i32, _P, _P, _P],
-    "fsf_gather_rows": [_P, c_i64, c_i32, _P, c_i64, _P, c_i64, _P],
-    "fsf_gather_rows_strided": [_P, c_i64, c_i64, c_i32, _P, c_i64, _P, c_i64, _P],
-    "fsf_gather_rows_add": [_P, c_i64, c_i64, c_i32, _P, c_i64, _P, c_i64, _P, c_i64, _P],
-    "fsf_norm_act": [_P, c_i64, c_i32, _P, _P, c_f32, c_i32, c_i32, _P, c_i64, _P],
-    "fsf_voxel2point": [_P, c_i32, _P, _P, c_i64, c_i32, _P, c_i64, _P, _P, c_f32, _P, _P, _P],
-    "fsf_voxel2point_strided": [_P, c_i32, _P, _P, c_i64, c_i32, _P, c_i64, _P, _P, c_f32, _P, c_i64, _P, _P],
-    "fsf_project_gather_mask": [_P, c_i64, c_i32, _P, c_i32, _P, c_i32, c_i32, c_i32, c_i32, _P, _P, _P],
-    "fsf_cam_select_score": [_P, c_i64, c_i32, c_i32, _P, c_i32, c_i32, c_i32, _P, _P, _P],
-    "fsf_project_score": [_P, c_i64, c_i32, _P, c_i32, _P, c_i32, c_i32, c_i32, c_i32, _P, c_i32, c_i32, c_i32, _P, _P, _P, _P, _P, _P],
-    "fsf_concat_mul": [_P, c_i64, c_i32, _P, _P, c_i64, c_i32, _P, c_i64, c_i32, c_f32, _P, c_i64, _P, _P],
-    "fsf_concat_mul_backward": [_P, c_i64, c_i32, _P, _P, c_i64, c_i32, _P, c_i64, c_i32, c_f32, _P, _P, c_i64, _P, _P, _P, _P],
-    "fsf_group_pairs_workspace_bytes": [c_i64, c_i32],
-    "fsf_group_pairs": [_P, c_i64, c_i32, c_i64, _P, c_i32, _P, c_i32, _P, _P, c_i64, _P, _P, c_i64, _P],
-    "fsf_overlap_plan_workspace_bytes": [c_i64],
-    "fsf_overlap_plan": [_P, _P, c_i64, c_i32, _P, _P, c_i64, _P],
-    "fsf_overlap_rows": [_P, c_i64, c_i32, _P, c_i32, _P, c_i32, c_i32, c_i32, c_i32, _P, _P, _P, c_i64, c_i64, c_i64, c_i64, _P, _P, _P],
-    "fsf_project_gather_bilinear": [_P, c_i64, c_i32, _P, c_i32, _P, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, _P, _P, _P],
-    "fsf_rulebook_workspace_bytes": [c_i64, c_i32],
-    "fsf_rulebook_subm": [_P, c_i64, c_i32, _P, _P, _P, _P, _P, c_i64, _P],
-    "fsf_rulebook_strided": [_P, c_i64, c_i32, _P, _P, _P, _P, _P, _P, c_i64, _P, _P, _P, _P, _P, c_i64, _P],
-    "fsf_rulebook_to_pairs_workspace_bytes": [c_i64, c_i32],
-    "fsf_rulebook_to_pairs": [_P, c_i64, c_i32, _P, c_i64, _P, _P, c_i64, _P],
-    "fsf_spconv_transpose_weight": [_P, c_i32, c_i32, c_i32, _P, _P],
-    "fsf_spconv_workspace_bytes": [c_i64, c_i32, c_i32, c_i32],
-    "fsf_spconv_forward": [_P, c_i64, c_i32, _P, c_i32, c_i32, _P, c_i64, _P, _P, _P, c_i32, _P, _P, c_i64, _P],
-    "fsf_spconv_backward_weight_workspace_bytes": [c_i64, c_i32, c_i32, c_i32],
-    "fsf_spconv_backward_weight": [_P, c_i64, c_i32, _P, c_i64, c_i32, _P, _P, c_i64, c_i32, _P, _P, c_i64, _P],
-    "fsf_connected_components_workspace_bytes": [c_i64],
-    "fsf_connected_components": [_P, c_i64, c_i32, _P, c_f32, _P, _P, _P, c_i64, _P],
-    "fsf_column_stats_workspace_bytes": [c_i32],
-    "fsf_column_stats": [_P, c_i64, c_i32, _P, _P, _P, c_i64, _P],
-    "fsf_batch_norm_train_stats": [_P, c_i64, c_i32, _P, _P, c_f32, c_f32, c_f32, c_f32, _P, _P, _P, _P, _P, _P, _P, _P, c_i64, _P],
-    "fsf_batch_norm_act_forward": [_P, c_i64, c_i32, _P, _P, c_i32, _P, _P],
-    "fsf_batch_norm_act_backward": [_P, _P, c_i64, c_i32, _P, _P, _P, _P, c_i32, _P, _P, _P, _P, c_i64, _P],
-    "fsf_norm_act_backward_workspace_bytes": [c_i32],
-    "fsf_norm_act_backward": [_P, _P, c_i64, c_i32, _P, _P, c_f32, c_i32, _P, _P, _P, _P, c_i64, _P],
-    "fsf_row_topk_desc": [_P, c_i64, c_i32, c_i32, _P, _P],
-    "fsf_sir_input_gather": [_P, c_i64, c_i32, _P, _P, _P, _P, c_i32, _P, c_i32, _P, c_i64, c_i32, c_f32, _P, c_i64, c_i32, c_f32, _P, _P, _P, c_i32,
-                             _P, _P, _P, c_i32, _P, _P, _P, c_f32, c_i32, c_i64, _P, c_i64, _P],
-    "fsf_sir_input": [_P, c_i64, c_i32, _P, _P, c_i64, c_i32, _P, c_i64, c_i32, c_f32, _P, c_i64, c_i32, c_f32, _P, _P, _P, c_i32,
-                      _P, _P, _P, c_i32, _P, _P, _P, c_f32, c_i32, c_i64, _P, c_i64, _P],
-    "fsf_spconv_split_weight_bytes": [c_i32, c_i32, c_i32],
-    "fsf_spconv_prepare_weight_split": [_P, c_i32, c_i32, c_i32, _P, _P],
-    "fsf_spconv_split_workspace_bytes": [c_i64, c_i32, c_i32, c_i32],
-    "fsf_spconv_forward_split": [_P, c_i64, c_i32, _P, c_i32, c_i32, _P, c_i64, _P, _P, _P, c_i32, _P, _P, c_i64, _P],
-    "fsf_planes_bytes": [c_i64, c_i32],
-    "fsf_planes_scale_count": [c_i64, c_i32],
-    "fsf_to_planes": [_P, c_i64, c_i32, c_i64, _P, _P, _P],
-    "fsf_to_planes_rows": [_P, c_i64, c_i32, c_i64, _P, _P, _P, _P],
-    "fsf_spconv_planes_weight_bytes": [c_i32, c_i32, c_i32],
-    "fsf_spconv_prepare_weight_planes": [_P, c_i32, c_i32, c_i32, _P, _P],
-    "fsf_spconv_forward_planes": [_P, _P, c_i32, _P, _P, c_i32, c_i64, _P, c_i32, c_i32, _P, c_i64, _P, _P, _P, c_i32, _P, _P, _P,
-                                  _P],
-    "fsf_channel_group_sum_add": [_P, c_i64, c_i32, c_i32, _P, _P, _P],
-    "fsf_channel_pair_sum_add2": [_P, c_i32, _P, c_i32, c_i64, _P, _P, _P],
-    "fsf_channel_pair_sum_add2_planes": [_P, c_i32, _P, c_i32, c_i64, _P, _P, _P, _P],
-    "fsf_linear_prepared_weight_bytes": [c_i32, c_i32],
-    "fsf_linear_prepare_weight": [_P, c_i32, c_i32, _P, _P],
-    "fsf_linear_norm_act": [_P, c_i64, c_i32, c_i64, _P, c_i32, _P, c_i32, _P, _P, c_f32, c_i32, _P, c_i64, _P],
-    "fsf_linear_prepared_weight_sliced_bytes": [c_i32, c_i32, c_i32],
-    "fsf_linear_prepare_weight_sliced": [_P, c_i32, c_i32, c_i32, _P, _P],
-    "fsf_linear_norm_act_sliced": [_P, c_i64, c_i32, c_i64, c_i64, _P, c_i32, c_i32, _P, c_i32, _P, _P, c_f32, c_i32, _P, c_i64, _P],
-    "fsf_linear_norm_act_grouped": [_P, c_i64, c_i32, c_i64, _P, c_i32, _P, _P, _P, c_i64, c_i32, _P, _P, c_f32, c_i32, _P,
-                                    c_i64, _P],
-    "fsf_linear_f16w_norm_act_grouped": [_P, c_i64, c_i32, c_i64, _P, c_i32, _P, _P, _P, c_i64, c_i32, _P, _P, c_f32, c_i32, _P,
-                                         c_i64, _P],
-    "fsf_linear_f16w_norm_act_segmax": [_P, c_i64, c_i32, c_i64, _P, c_i32, _P, _P, _P, c_i64, c_i32, _P, _P, c_f32, c_i32, _P, c_i64,
-                                        _P, c_i64, _P, c_i64, _P],
-    "fsf_dynamic_point_pool_workspace_bytes": [c_i64, c_i64],
-    "fsf_dynamic_point_pool": [_P, c_i64, c_i32, c_i32, c_i32, _P, c_i64, c_i32, _P, _P, c_i32, c_i64, _P, _P, _P, _P, _P,
-                               _P, c_i64, _P],
-    "fsf_nms_bev_workspace_bytes": [c_i64],
-    "fsf_nms_bev": [_P, c_i64, c_f32, c_i32, _P, _P, _P, _P, c_i64, _P],
-    "fsf_nms_bev_multiclass_workspace_bytes": [c_i64, c_i32],
-    "fsf_nms_bev_multiclass": [_P, c_i64, c_i32, _P, _P, c_f32, c_i32, _P, _P, _P, c_i64, _P],
-    "fsf_nms_bev_multiclass_capped": [_P, c_i64, c_i32, _P, _P, c_f32, c_i32, c_i64, _P, _P, _P, _P, c_i64, _P],
-    "fsf_nms_bev_multiclass_capped_workspace_bytes": [c_i64, c_i32, c_i64],
-    "fsf_decode_cluster_boxes": [_P, c_i64, _P, c_i64, _P, c_i64, c_i64, c_i32, c_i32, c_f32, _P, _P, _P, _P],
-    "fsf_class_rank_desc_workspace_bytes": [c_i64, c_i32],
-    "fsf_class_rank_desc": [_P, c_i64, c_i32, c_f32, _P, _P, _P, _P, c_i64, _P],
-    "fsf_linear_norm_act_segmax": [_P, c_i64, c_i32, c_i64, _P, c_i32, _P, _P, _P, c_i64, c_i32, _P, _P, c_f32, c_i32, _P, c_i64,
-                                   _P, c_i64, _P, c_i64, _P],
-    "fsf_nms_select_capacity": [],
-    "fsf_box_tail_max_classes": [],
-    "fsf_nms_select": [_P, c_i32, _P, _P, _P, c_i64, _P, c_i64, c_i32, c_i64, c_i32, _P, _P, _P, _P, _P],
-    "fsf_connected_components_grouped": [_P, c_i64, c_i32, _P, _P, c_i32, _P, _P, _P, c_i64, _P],
-    "fsf_cluster_key_survival_workspace_bytes": [c_i64, c_i64],
-    "fsf_cluster_key_survival": [_P, c_i32, _P, c_i64, _P, c_i64, c_i64, c_i64, c_i32, _P, _P, _P, _P, _P, _P, c_i64, _P],
-    "fsf_cluster_point_ids": [_P, _P, c_i64, _P, _P, _P, c_i64, c_i32, _P, _P, c_i64, _P],
-    "fsf_ingroup_rank_workspace_bytes": [c_i64],
-    "fsf_ingroup_rank": [_P, c_i64, _P, _P, c_i64, _P],
-    "fsf_order_by_neighbor_mask_workspace_bytes": [c_i64],
-    "fsf_order_by_neighbor_mask": [_P, c_i64, c_i32, _P, _P, _P, _P, c_i64, _P],
-    "fsf_remap_indices": [_P, c_i64, _P, _P, _P],
-    "fsf_set_option": [c_i32, c_i64],
-    "fsf_get_option": [c_i32],
-    "fsf_row_planes_bytes": [c_i64, c_i32],
-    "fsf_rows_to_planes": [_P, c_i64, c_i32, c_i64, c_i32, _P, _P, c_f32, c_i32, _P, _P, _P, c_i64, _P],
-    "fsf_linear_prepared_weight_f16_bytes": [c_i32, c_i32, c_i32],
-    "fsf_linear_prepare_weight_f16": [_P, c_i32, c_i32, c_i32, _P, _P],
-    "fsf_linear_planes_norm_act": [_P, _P, c_i64, c_i32, _P, c_i32, c_i32, _P, c_i32, _P, _P, c_f32, c_i32, _P, c_i64, _P],
-    "fsf_spconv_split_weight_f16_bytes": [c_i32, c_i32, c_i32],
-    "fsf_spconv_prepare_weight_split_f16": [_P, c_i32, c_i32, c_i32, _P, _P],
-    "fsf_spconv_forward_split_planes": [_P, _P, c_i64, c_i32, _P, c_i32, c_i32, _P, c_i64, _P, _P, _P, c_i32, _P, _P, c_i64, _P],
-    "fsf_sir_stack_arena_bytes": [_P, c_i32, c_i64, c_i64],
-    "fsf_sir_stack_forward": [_P, c_i32, _P, c_i64, c_i32, _P, _P, _P, c_i32, _P, c_i32, _P, c_i64, c_i32, c_f32, _P, c_i64, c_i32, _P, c_i64,
-                              c_i64, _P, c_i64, _P, _P, c_i64, _P],
-    "fsf_sorted_rows": [_P, _P, c_i64, _P, c_i64, c_i32, _P, c_i64, _P, c_i64, _P, _P, _P, _P, _P, _P, c_i64, c_f32, _P],
-    "fsf_compact_pairs": [_P, c_i64, _P, c_i64, _P, _P, _P, _P, _P, _P, c_i64, _P, _P, _P, _P, _P],
-    "fsf_combine_queries": [_P, c_i64, _P, c_i64, _P, _P, _P, c_i32, c_i64, _P, _P, _P, _P],
-    "fsf_decode_rois": [_P, c_i64, c_i32, _P, c_i64, _P, c_i64, c_i64, c_f32, _P, _P],
-    "fsf_refine_rows": [_P, _P, c_i64, c_i32, _P, _P, _P, c_i64, c_i64, _P, _P, _P],
-    "fsf_encode_preds_2d": [_P, c_i64, c_i32, _P, c_i64, c_i32, c_f32, c_f32, _P, _P, c_i64, _P],
-    "fsf_weighted_xyz": [_P, c_i64, _P, c_i64, c_f32, _P, _P],
-    "fsf_centroid_divide": [_P, c_i64, _P, _P],
-    "fsf_lidar_cluster_frontend_arena_bytes": [c_i64, c_i32, c_i32],
-    "fsf_lidar_cluster_frontend": [_P, c_i64, c_i32, c_i64, _P, c_i32, _P, _P, c_i32, _P, c_i32, _P, c_i32, c_i32, _P, _P, _P, _P, _P, c_i64, _P,
-                                   _P, c_i64, _P, _P],
-}
-_configured = False
+ERR_KEY_RANGE = _lib.DEFINES["FSF_ERR_KEY_RANGE"]
 
 
 def _L():
-    global _configured
-    h = _lib.lib()
-    if not _configured:
-        for name, argtypes in _ARGTYPES.items():
-            getattr(h, name).argtypes = argtypes
-        _configured = True
-    return h
+    """The library handle every wrapper calls through (tools/profiling/host_gaps.py swaps this function for a timing proxy)."""
+    return _lib.lib()
 
 
 def _rows_view(t):
@@ -505,7 +352,6 @@ def unique_rows(coors: torch.Tensor, col_min: Optional[Sequence[int]] = None, co
     ws = _lib.workspace(ws_bytes, dev)
     cmin = i64_array(col_min) if col_min is not None else None
     cmax = i64_array(col_max) if col_max is not None else None
-    import ctypes
     check(h.fsf_unique_rows(ptr(coors), n, k, cmin, cmax, ptr(new_coors), ptr(inv), ptr(cnt), ptr(order),
                             ptr(seg_offsets), ptr(m_dev), ctypes.cast(ctypes.pointer(m_host), c_p), ptr(ws),
                             ws.numel(), stream_ptr()), "fsf_unique_rows")
@@ -1458,7 +1304,7 @@ def linear_planes_norm_act(xp: RowPlanes, wplanes: torch.Tensor, out_features: i
 
 
 # ----------------------------------------------------------------------------------- refine-stage ops
-OPT_POOL_BRUTE = 1
+OPT_POOL_BRUTE = _lib.DEFINES["FSF_OPT_POOL_BRUTE"]
 
 
 def set_option(option: int, value: int) -> int:
@@ -1826,6 +1672,9 @@ def sorted_rows(order, inv, points, f_cluster=None, centers=None, index=None, fi
     return seg_ids, pts_s, fcl_s, idx_s
 
 
+_SIR_MAX_LAYERS = _lib.DEFINES["FSF_SIR_MAX_LAYERS"]
+
+
 class _SirLayerC(ctypes.Structure):  # FsfSirLayer (include/fsf_hip.h)
     _fields_ = [("planes_left", ctypes.c_void_p), ("planes_right", ctypes.c_void_p), ("left_f16", ctypes.c_int32), ("right_f16", ctypes.c_int32),
                 ("bias", ctypes.c_void_p), ("gamma", ctypes.c_void_p), ("beta", ctypes.c_void_p), ("eps", ctypes.c_float),
@@ -1837,7 +1686,7 @@ class _SirBlockC(ctypes.Structure):  # FsfSirBlock
                 ("b2", ctypes.c_void_p), ("w3", ctypes.c_void_p), ("g3", ctypes.c_void_p), ("b3", ctypes.c_void_p),
                 ("h1", ctypes.c_int32), ("h2", ctypes.c_int32), ("mlp_eps", ctypes.c_float), ("mlp_act", ctypes.c_int32),
                 ("xyz_normalizer", ctypes.c_float * 3), ("rel_div", ctypes.c_float), ("in_cols", ctypes.c_int32),
-                ("num_layers", ctypes.c_int32), ("layer", _SirLayerC * 4)]
+                ("num_layers", ctypes.c_int32), ("layer", _SirLayerC * _SIR_MAX_LAYERS)]
 
 
 class SirStackDescriptor:
@@ -1868,7 +1717,7 @@ class SirStackDescriptor:
             k.h1, k.h2, k.mlp_eps, k.mlp_act = w1.size(0), w2.size(0), float(b["mlp_eps"]), codes_a[b["mlp_act"]]
             k.xyz_normalizer = (ctypes.c_float * 3)(*[float(v) for v in b["xyz_normalizer"]])
             k.rel_div, k.in_cols, k.num_layers = float(b["rel_div"]), int(b["in_cols"]), len(b["layers"])
-            assert 1 <= len(b["layers"]) <= 4
+            assert 1 <= len(b["layers"]) <= _SIR_MAX_LAYERS
             for i, l in enumerate(b["layers"]):
                 L = k.layer[i]
                 L.planes_left, L.left_f16 = dp(l["planes_left"]), int(linear_weight_is_f16(l["planes_left"]))
@@ -2032,21 +1881,24 @@ def lidar_cluster_frontend(scores, thresh, group_cols, logits, offsets, points, 
     nbytes = int(h.fsf_lidar_cluster_frontend_arena_bytes(m, ng, pc))
     arena = torch.empty((nbytes,), dtype=torch.uint8, device=pt.device)
     assert arena.data_ptr() % 256 == 0
-    out = (ctypes.c_int64 * 16)()
+    defs = _lib.DEFINES
+    out = (ctypes.c_int64 * defs["FSF_LCF_OUT_WORDS"])()
     check(h.fsf_lidar_cluster_frontend(sp, m, int(num_classes), ss, ptr(thresh.contiguous()), ng, masks, lp, ls, op, os_, pp, ps, pc,
                                        ptr(batch_idx), vs, f32_array(range_min), i64_array(key_min), i64_array(key_max), int(min_points),
                                        ptr(dist_table.contiguous()), ptr(arena), nbytes, ctypes.cast(out, c_p), stream_ptr()),
           "fsf_lidar_cluster_frontend")
-    P, K, Kk, V, C = (int(out[i]) for i in range(5))
+    P, K, Kk, V, C = (int(out[defs["FSF_LCF_" + k]]) for k in ("PAIRS", "KEYS", "KEPT_KEYS", "ROWS", "CLUSTERS"))
 
-    def view(slot, dtype, shape):
-        off, n = int(out[slot]), 1
+    def view(slot, dtype, shape):  # the result whose arena byte offset is out[FSF_LCF_OFF_<slot>]
+        off, n = int(out[defs["FSF_LCF_OFF_" + slot]]), 1
         for d in shape:
             n *= d
         return arena[off:off + n * torch.empty((), dtype=dtype).element_size()].view(dtype).view(shape)
 
-    inv = view(10, torch.int64, (V,))
-    plan = SegmentPlan(inv=inv, order=view(12, torch.int32, (V,)), seg_offsets=view(13, torch.int32, (C + 1,)), m=C, cnt=view(11, torch.int64, (C,)))
-    return dict(p_ids=view(5, torch.int64, (V,)), centers=view(6, torch.float32, (V, 3)), cluster_inds=view(7, torch.int64, (V, 3)),
-                points=view(8, torch.float32, (V, pc)), new_coors=view(9, torch.int64, (C, 3)), plan=plan,
-                cluster_xyz=view(14, torch.float32, (C, 3)), counts=dict(pairs=P, keys=K, kept_keys=Kk, rows=V, clusters=C))
+    inv = view("INV", torch.int64, (V,))
+    plan = SegmentPlan(inv=inv, order=view("ORDER", torch.int32, (V,)), seg_offsets=view("SEG_OFFSETS", torch.int32, (C + 1,)), m=C,
+                       cnt=view("CNT", torch.int64, (C,)))
+    return dict(p_ids=view("P_IDS", torch.int64, (V,)), centers=view("CENTERS", torch.float32, (V, 3)),
+                cluster_inds=view("CLUSTER_INDS", torch.int64, (V, 3)), points=view("POINTS", torch.float32, (V, pc)),
+                new_coors=view("NEW_COORS", torch.int64, (C, 3)), plan=plan, cluster_xyz=view("CLUSTER_XYZ", torch.float32, (C, 3)),
+                counts=dict(pairs=P, keys=K, kept_keys=Kk, rows=V, clusters=C))

@@ -1,5 +1,5 @@
-"""CPU: the C-ABI library builds for gfx950, loads, and exports every symbol include/fsf_hip.h declares.
-No compute calls (there is no GPU in the build container)."""
+"""CPU: the C-ABI library builds for gfx950, loads, and exports every symbol include/fsf_hip.h declares; the ctypes signatures,
+constants and descriptor structs the package uses are the header's.  No compute calls (there is no GPU in the build container)."""
 import ctypes
 import os
 import re
@@ -7,12 +7,14 @@ import re
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+HEADER = os.path.join(ROOT, "include", "fsf_hip.h")
+P, I32, I64, F32 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_float
 
 
 def declared_symbols():
-    text = open(os.path.join(ROOT, "include", "fsf_hip.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    return sorted(set(re.findall(r"\b(fsf_[a-z0-9_]+)\s*\(", text)))
+    from fullysparsefusion_amd import _lib
+
+    return sorted(_lib.SIGNATURES)
 
 
 def test_header_declares_the_hot_path():
@@ -25,7 +27,7 @@ def test_header_declares_the_hot_path():
 
 
 def test_library_builds_and_exports_every_declared_symbol():
-    from fullysparsefusion_amd import build
+    from fullysparsefusion_amd import _lib, build
 
     lib_path = build.build()
     assert os.path.exists(lib_path)
@@ -34,15 +36,102 @@ def test_library_builds_and_exports_every_declared_symbol():
     assert not missing, f"declared in include/fsf_hip.h but not exported: {missing}"
     lib.fsf_status_string.restype = ctypes.c_char_p
     assert lib.fsf_status_string(0) == b"ok"
-    header = int(re.search(r"#define\s+FSF_ABI_VERSION\s+(\d+)", open(os.path.join(ROOT, "include", "fsf_hip.h")).read()).group(1))
+    header = _lib.DEFINES["FSF_ABI_VERSION"]
     assert lib.fsf_abi_version() == header  # (the loader in fullysparsefusion_amd/_lib.py refuses a library of another version)
 
 
-def test_wrapper_argtypes_cover_the_header():
+def test_every_declared_function_is_bound_to_its_header_signature():
+    from fullysparsefusion_amd import _lib, build, hip_ops
+
+    build.build()
+    text = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
+    assert sorted(set(re.findall(r"\b(fsf_[a-z0-9_]+)\s*\(", text))) == declared_symbols()  # (the reader skips no declaration)
+    h = _lib.lib()
+    assert hip_ops._L() is h
+    for name, (argtypes, restype) in _lib.SIGNATURES.items():
+        fn = getattr(h, name)
+        assert list(fn.argtypes) == argtypes and fn.restype is restype, name
+
+
+def test_signature_rules_on_pinned_declarations():
+    from fullysparsefusion_amd._lib import SIGNATURES
+
+    # arrays (`const float voxel_size[3]`) and `void* stream` are pointers
+    assert SIGNATURES["fsf_voxelize_dynamic"] == ([P, I64, I32, I32, P, P, P, P, P, P], I32)
+    # `const FsfSirBlock*`, `const float* const*`
+    assert SIGNATURES["fsf_sir_stack_forward"] == ([P, I32, P, I64, I32, P, P, P, I32, P, I32, P, I64, I32, F32, P, I64, I32, P, I64, I64, P,
+                                                    I64, P, P, I64, P], I32)
+    assert SIGNATURES["fsf_weighted_xyz"] == ([P, I64, P, I64, F32, P, P], I32)
+    assert SIGNATURES["fsf_lidar_cluster_frontend_arena_bytes"] == ([I64, I32, I32], I64)
+    assert SIGNATURES["fsf_augment_max"] == ([], I32)
+    assert SIGNATURES["fsf_status_string"] == ([I32], ctypes.c_char_p)
+
+
+SMALL_HEADER = """
+#ifndef FSF_SMALL_H_
+#define FSF_SMALL_H_
+#define FSF_ONE 1
+#define FSF_ERR_SMALL (-7)   /* negative */
+/* int fsf_commented_out(double x); */
+extern "C" {
+int64_t fsf_size(int64_t n,
+                 int32_t k);  // a declaration over two lines
+"""
+
+
+def test_reader_on_a_small_header():
+    from fullysparsefusion_amd._lib import parse_header
+
+    assert parse_header(SMALL_HEADER) == ({"fsf_size": ([I64, I32], I64)}, {"FSF_ONE": 1, "FSF_ERR_SMALL": -7})
+
+
+@pytest.mark.parametrize("decl, typ", [("int fsf_bad(uint32_t flags);", "uint32_t"), ("int fsf_bad(int64_t n, double x);", "double"),
+                                       ("int fsf_bad(FsfSirBlock block);", "FsfSirBlock"), ("double fsf_bad(void);", "double"),
+                                       ("void fsf_bad(int32_t n);", "void")])
+def test_reader_refuses_a_type_it_cannot_bind(decl, typ):
+    from fullysparsefusion_amd._lib import FsfHipError, parse_header
+
+    with pytest.raises(FsfHipError, match=f"fsf_bad: .*'{typ}'"):
+        parse_header(SMALL_HEADER + decl)
+
+
+def test_int64_results_above_2_to_the_31_come_back_whole():
+    """An int64_t result bound with ctypes' default int return type loses its upper half: K30's arena size for 10^6 rows, six groups
+    (2 337 766 912 bytes) once read back as -1 957 200 384."""
+    from fullysparsefusion_amd import _lib, build, hip_ops
+
+    build.build()
+    assert _lib.lib().fsf_lidar_cluster_frontend_arena_bytes(1_000_000, 6, 5) == 2_337_766_912
+    assert hip_ops._L().fsf_lidar_cluster_frontend_arena_bytes(1_000_000, 6, 5) == 2_337_766_912
+
+
+def header_structs():
+    """{name: [(field, is_pointer, base type, array extent or None)]} of every `typedef struct { ... } name;` of the header."""
+    from fullysparsefusion_amd._lib import DEFINES
+
+    text = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
+    structs = {}
+    for body, name in re.findall(r"typedef\s+struct\s*\{(.*?)\}\s*(\w+)\s*;", text, flags=re.S):
+        fields = []
+        for decl in filter(None, (d.strip() for d in body.split(";"))):
+            first, *rest = decl.split(",")  # `const float *bias, *gamma, *beta`: one base type, several declarators
+            base, first = re.fullmatch(r"(.*?)\s*(\**\s*\w+(?:\[\w+\])?)", first.strip()).groups()
+            for d in [first] + rest:
+                star, field, ext = re.fullmatch(r"\s*(\*?)\s*(\w+)(?:\[(\w+)\])?\s*", d).groups()
+                fields.append((field, star == "*", base, int(DEFINES.get(ext, ext)) if ext else None))
+        structs[name] = fields
+    return structs
+
+
+def test_sir_descriptor_structs_match_the_header():
     from fullysparsefusion_amd import hip_ops
 
-    declared = set(declared_symbols()) - {"fsf_status_string", "fsf_abi_version"}
-    assert declared == set(hip_ops._ARGTYPES), declared ^ set(hip_ops._ARGTYPES)
+    structs = header_structs()
+    scalar = {"int32_t": ctypes.c_int32, "float": ctypes.c_float, "FsfSirLayer": hip_ops._SirLayerC}
+    for cls, name in ((hip_ops._SirLayerC, "FsfSirLayer"), (hip_ops._SirBlockC, "FsfSirBlock")):
+        want = [(f, P if ptr else scalar[base], ext) for f, ptr, base, ext in structs[name]]
+        got = [(f, t._type_, t._length_) if issubclass(t, ctypes.Array) else (f, t, None) for f, t in cls._fields_]
+        assert got == want, name
 
 
 def test_product_path_fails_loudly_without_a_gpu():

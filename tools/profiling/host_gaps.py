@@ -14,7 +14,7 @@ dev = torch.device("cuda:0")
 model = bench.build_model(dev)
 frames = [bench.make_inputs(sweeps, s, dev)[1] for s in (0, 131, 262, 393)]
 log = []
-real = hip_ops._L()  # (argtypes configured)
+real = hip_ops._L()
 
 
 class Proxy:

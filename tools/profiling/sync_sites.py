@@ -33,11 +33,12 @@ class Spy(TorchDispatchMode):
                 site("d2h copy")
         return func(*args, **(kwargs or {}))
 
-# the library counts its own stream waits (FSF_OPT_HOST_WAITS = 2): the difference across a C-ABI call is what that call waited
+# the library counts its own stream waits (FSF_OPT_HOST_WAITS): the difference across a C-ABI call is what that call waited
+HOST_WAITS = _lib.DEFINES["FSF_OPT_HOST_WAITS"]
 orig = _lib.check
-state = dict(last=int(_lib.lib().fsf_get_option(2)))
+state = dict(last=int(_lib.lib().fsf_get_option(HOST_WAITS)))
 def check(status, what):
-    now = int(_lib.lib().fsf_get_option(2))
+    now = int(_lib.lib().fsf_get_option(HOST_WAITS))
     for _ in range(now - state["last"]):
         site("C-ABI read-back " + what)
     state["last"] = now
