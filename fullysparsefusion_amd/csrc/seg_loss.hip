@@ -7,12 +7,13 @@
 //   fsf_seg_loss_backward  (K35c): dense grad_logits / grad_votes; the softmax is recomputed.  Per-row stats go to LDS, then the
 //                                  workgroup writes its block of rows as one contiguous range.
 // No float atomics and no host synchronisation: the same inputs give bit-identical outputs from run to run.
+#include "box_contain.h"
 #include "common.h"
 
 namespace fsf {
 
 constexpr int SL_BLOCK = 256;
-constexpr int SL_BOX_WORDS = 8;   // (cx, cy, cz, half_w, half_l, half_h, cosa, sina)
+constexpr int SL_BOX_WORDS = BOX_WORDS;  // (cx, cy, cz, half_w, half_l, half_h, cosa, sina): box_contain.h
 constexpr int SL_FINAL_BLOCK = 256;
 
 // ------------------------------------------------------------------------------------------------ K35a
@@ -22,17 +23,7 @@ __global__ void __launch_bounds__(SL_BLOCK) seg_box_prep_kernel(const float* __r
   const int64_t k = (int64_t)blockIdx.x * SL_BLOCK + threadIdx.x;
   if (k >= num_boxes) return;
   const float* b = boxes + k * box_stride;
-  const float h = b[5];
-  const double yaw = -(double)b[6];
-  float* t = table + k * SL_BOX_WORDS;
-  t[0] = b[0];
-  t[1] = b[1];
-  t[2] = __fadd_rn(b[2], h * 0.5f);
-  t[3] = b[3] * 0.5f;
-  t[4] = b[4] * 0.5f;
-  t[5] = h * 0.5f;
-  t[6] = (float)cos(yaw);
-  t[7] = (float)sin(yaw);
+  box_constants(b[0], b[1], b[2], b[3], b[4], b[5], b[6], table + k * SL_BOX_WORDS);
 }
 
 template <typename BT>
@@ -49,23 +40,7 @@ __global__ void __launch_bounds__(SL_BLOCK) seg_targets_kernel(const float* __re
     const float* p = points + i * pt_stride;
     const float px = p[0], py = p[1], pz = p[2];
     const int64_t b = (int64_t)batch_idx[i];
-    int hit = -1;
-    if (b >= 0 && b < num_samples) {
-      const int k1 = box_ptr[b + 1];
-      for (int k = box_ptr[b]; k < k1; ++k) {
-        if (box_labels[k] < 0) continue;  // dropped GT rows (the reference filters them before points_in_boxes)
-        const float* t = table + (int64_t)k * SL_BOX_WORDS;
-        if (fabsf(__fsub_rn(pz, t[2])) > t[5]) continue;
-        const float sx = __fsub_rn(px, t[0]), sy = __fsub_rn(py, t[1]);
-        const float cosa = t[6], sina = t[7];
-        const float lx = __fadd_rn(__fmul_rn(sx, cosa), __fmul_rn(sy, -sina));
-        const float ly = __fadd_rn(__fmul_rn(sx, sina), __fmul_rn(sy, cosa));
-        if (lx > -t[4] && lx < t[4] && ly > -t[3] && ly < t[3]) {
-          hit = k;
-          break;
-        }
-      }
-    }
+    const int hit = (b >= 0 && b < num_samples) ? first_box_containing(px, py, pz, table, box_labels, box_ptr[b], box_ptr[b + 1]) : -1;
     float d[3] = {0.f, 0.f, 0.f};
     int64_t lab = num_classes;
     if (hit >= 0) {

@@ -240,6 +240,109 @@ def seg_loss_backward(logits: torch.Tensor, votes: torch.Tensor, labels: torch.T
     return grad_logits, grad_votes
 
 
+def cluster_targets(cluster_xyz: torch.Tensor, batch_idx: torch.Tensor, box_ptr: torch.Tensor, boxes: torch.Tensor,
+                    box_labels: torch.Tensor, num_classes: int, code_size: int, enlarge_width: float = 0.0):
+    """fsf_cluster_targets (K36a): cluster centres f32 [n, >=3], batch_idx i32 / i64 [n] (any element stride: a column of the cluster
+    index table), per-sample CSR box_ptr i32 [B + 1], boxes f32 [M, 7 | 9 | 10] in the task's order, box_labels i32 [M] (task labels,
+    rows < 0 skipped) -> (labels i64 [n], bbox_targets f32 [n, code], bbox_weights f32 [n, code], assigned i32 [n], stats f32 [6] =
+    (num_preds, num_pos_preds, num_gts, assigned_gts, cls_avg_factor, reg_avg_factor)), all on the device.  No sync."""
+    require_cuda(cluster_xyz, batch_idx, box_ptr, boxes, box_labels)
+    assert cluster_xyz.dtype == torch.float32 and cluster_xyz.dim() == 2 and cluster_xyz.size(1) >= 3
+    if cluster_xyz.stride(1) != 1:
+        cluster_xyz = cluster_xyz.contiguous()
+    assert batch_idx.dtype in (torch.int32, torch.int64) and batch_idx.dim() == 1 and batch_idx.numel() == cluster_xyz.size(0)
+    assert box_ptr.dtype == torch.int32 and box_ptr.dim() == 1 and box_ptr.numel() >= 1
+    assert boxes.dtype == torch.float32 and boxes.dim() == 2 and boxes.stride(1) == 1
+    assert box_labels.dtype == torch.int32 and box_labels.dim() == 1 and box_labels.numel() == boxes.size(0)
+    n, m, dev = cluster_xyz.size(0), boxes.size(0), cluster_xyz.device
+    code = int(code_size)
+    assert code in (8, 10) and (m == 0 or (boxes.size(1) in (7, 9, 10) and (boxes.size(1) == 7) == (code == 8))), \
+        "the coder appends box columns 7, 8 exactly when the boxes have them (7 columns <-> code size 8)"
+    if n > 1 and batch_idx.stride(0) < 1:
+        batch_idx = batch_idx.contiguous()
+    box_ptr, box_labels = box_ptr.contiguous(), box_labels.contiguous()
+    labels = torch.empty((n,), dtype=torch.int64, device=dev)
+    targets = torch.empty((n, code), dtype=torch.float32, device=dev)
+    weights = torch.empty((n, code), dtype=torch.float32, device=dev)
+    assigned = torch.empty((n,), dtype=torch.int32, device=dev)
+    stats = torch.empty((6,), dtype=torch.float32, device=dev)
+    h = _L()
+    ws = _lib.workspace(h.fsf_cluster_targets_workspace_bytes(m, n), dev)
+    check(h.fsf_cluster_targets(c_p(cluster_xyz.data_ptr()) if n else c_p(None), n, cluster_xyz.stride(0) if n > 1 else 3,
+                                c_p(batch_idx.data_ptr()) if n else c_p(None), batch_idx.element_size(),
+                                batch_idx.stride(0) if n > 1 else 1, ptr(box_ptr), box_ptr.numel() - 1,
+                                c_p(boxes.data_ptr()) if m else c_p(None), m, boxes.stride(0) if m > 1 else max(boxes.size(1), 7),
+                                boxes.size(1) if m else 7, ptr(box_labels), int(num_classes), code, float(enlarge_width), ptr(ws),
+                                ws.numel(), ptr(labels), ptr(targets), ptr(weights), ptr(assigned), ptr(stats), stream_ptr()),
+          "fsf_cluster_targets")
+    return labels, targets, weights, assigned, stats
+
+
+def _cluster_loss_operands(cls_logits, reg_preds, labels, label_weights, bbox_targets, bbox_weights, avg_factors):
+    require_cuda(cls_logits, reg_preds, labels, label_weights, bbox_targets, bbox_weights, avg_factors)
+    assert cls_logits.dtype == torch.float32 and cls_logits.dim() == 2 and reg_preds.dtype == torch.float32 and reg_preds.dim() == 2
+    cls_logits, ld_c = _rows_view(cls_logits)
+    reg_preds, ld_r = _rows_view(reg_preds)
+    n, c = cls_logits.shape
+    code = reg_preds.size(1)
+    assert reg_preds.size(0) == n and code in (8, 10)
+    assert labels.dtype == torch.int64 and labels.dim() == 1 and labels.numel() == n
+    assert bbox_targets.dtype == torch.float32 and bbox_targets.shape == (n, code)
+    assert bbox_weights.dtype == torch.float32 and bbox_weights.shape == (n, code)
+    assert avg_factors.dtype == torch.float32 and avg_factors.numel() == 2
+    if label_weights is not None:
+        assert label_weights.dtype == torch.float32 and label_weights.numel() == n
+        label_weights = label_weights.contiguous()
+    if n <= 1:
+        ld_c, ld_r = c, code
+    return (cls_logits, ld_c, reg_preds, ld_r, n, c, code, labels.contiguous(), label_weights, bbox_targets.contiguous(),
+            bbox_weights.contiguous(), avg_factors.contiguous())
+
+
+def cluster_loss_forward(cls_logits: torch.Tensor, reg_preds: torch.Tensor, labels: torch.Tensor, label_weights, bbox_targets: torch.Tensor,
+                         bbox_weights: torch.Tensor, avg_factors: torch.Tensor, gamma: float, alpha: float, loss_weights, with_vel: bool):
+    """fsf_cluster_loss_forward (K36b): cls_logits f32 [n, C] and reg_preds f32 [n, 8 | 10] (own row strides), labels i64 [n] (positive
+    when in [0, C)), label_weights f32 [n] | None, bbox_targets / bbox_weights f32 [n, code], avg_factors f32 [2] (cls, reg) on the
+    device, loss_weights = (cls, center, size, rot, vel) -> (losses f32 [5] = (cls, center, size, rot, vel), counts i64 [1] = positive
+    rows).  No sync."""
+    cls_logits, ld_c, reg_preds, ld_r, n, c, code, labels, label_weights, bbox_targets, bbox_weights, avg_factors = _cluster_loss_operands(
+        cls_logits, reg_preds, labels, label_weights, bbox_targets, bbox_weights, avg_factors)
+    dev = cls_logits.device
+    losses = torch.empty((5,), dtype=torch.float32, device=dev)
+    counts = torch.empty((1,), dtype=torch.int64, device=dev)
+    h = _L()
+    ws = _lib.workspace(h.fsf_cluster_loss_workspace_bytes(n), dev)
+    nz = lambda t: c_p(t.data_ptr()) if n else c_p(None)  # noqa: E731
+    check(h.fsf_cluster_loss_forward(nz(cls_logits), ld_c, nz(reg_preds), ld_r, n, c, code, ptr(labels), ptr(label_weights), ptr(bbox_targets),
+                                     ptr(bbox_weights), ptr(avg_factors), float(gamma), float(alpha), *[float(w) for w in loss_weights],
+                                     int(bool(with_vel)), ptr(ws), ws.numel(), ptr(losses), ptr(counts), stream_ptr()),
+          "fsf_cluster_loss_forward")
+    return losses, counts
+
+
+def cluster_loss_backward(cls_logits: torch.Tensor, reg_preds: torch.Tensor, labels: torch.Tensor, label_weights, bbox_targets: torch.Tensor,
+                          bbox_weights: torch.Tensor, avg_factors: torch.Tensor, gamma: float, alpha: float, loss_weights, with_vel: bool,
+                          counts: torch.Tensor, grads):
+    """fsf_cluster_loss_backward (K36c): the operands of cluster_loss_forward, its `counts` and the upstream gradients of the five
+    losses (`grads`: five f32 one-element device tensors, None = 0) -> dense (grad_cls_logits f32 [n, C], grad_reg_preds f32 [n, code]).
+    The sigmoid is recomputed.  No sync."""
+    cls_logits, ld_c, reg_preds, ld_r, n, c, code, labels, label_weights, bbox_targets, bbox_weights, avg_factors = _cluster_loss_operands(
+        cls_logits, reg_preds, labels, label_weights, bbox_targets, bbox_weights, avg_factors)
+    require_cuda(counts, *grads)
+    assert counts.dtype == torch.int64 and counts.numel() == 1 and len(grads) == 5
+    assert all(g is None or (g.dtype == torch.float32 and g.numel() == 1) for g in grads)
+    dev = cls_logits.device
+    grad_cls = torch.empty((n, c), dtype=torch.float32, device=dev)
+    grad_reg = torch.empty((n, code), dtype=torch.float32, device=dev)
+    if n:
+        check(_L().fsf_cluster_loss_backward(c_p(cls_logits.data_ptr()), ld_c, c_p(reg_preds.data_ptr()), ld_r, n, c, code, ptr(labels),
+                                             ptr(label_weights), ptr(bbox_targets), ptr(bbox_weights), ptr(avg_factors), float(gamma),
+                                             float(alpha), *[float(w) for w in loss_weights], int(bool(with_vel)), ptr(counts.contiguous()),
+                                             *[c_p(None) if g is None else c_p(g.data_ptr()) for g in grads], ptr(grad_cls),
+                                             ptr(grad_reg), stream_ptr()), "fsf_cluster_loss_backward")
+    return grad_cls, grad_reg
+
+
 def voxelize_dynamic(points: torch.Tensor, voxel_size, pc_range, grid, batch_idx: int = 0, want_zyx=True,
                      want_bzyx=False):
     """fsf_voxelize_dynamic.  points f32 [n, C>=3] -> (coors_zyx i32 [n,3] | None, coors_bzyx i64 [n,4] | None)."""

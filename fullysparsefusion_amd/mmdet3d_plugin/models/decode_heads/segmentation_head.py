@@ -82,32 +82,36 @@ def seg_targets_host(points, gt_boxes, gt_labels, bg_label):
     return this_label, encode_vote_targets(delta), ~bg
 
 
-def pack_gt_for_device(gt_bboxes_list, gt_labels_list, device):
-    """Per-sample GT -> (box_ptr i32 [B + 1], boxes f32 [M, 7], labels i32 [M]) on `device` with no host wait: CPU boxes and labels
+def pack_gt_for_device(gt_bboxes_list, gt_labels_list, device, cols=7):
+    """Per-sample GT -> (box_ptr i32 [B + 1], boxes f32 [M, cols], labels i32 [M]) on `device` with no host wait: CPU boxes and labels
     travel in ONE pinned buffer and one non-blocking copy; device boxes are concatenated where they are (only the CSR offsets, known
-    from the shapes, are uploaded)."""
+    from the shapes, are uploaded).  `cols=None` keeps every column of the rows (all non-empty samples must have the same number)."""
     rows = [gt_box_rows(b) for b in gt_bboxes_list]
     labs = [torch.as_tensor(l).reshape(-1) for l in gt_labels_list]
     counts = [int(r.shape[0]) for r in rows]
     assert all(int(l.numel()) == c for l, c in zip(labs, counts)), "one label per GT box"
+    if cols is None:
+        widths = {int(r.shape[1]) for r in rows if r.shape[0]}
+        assert len(widths) <= 1, f"GT rows of one batch differ in their number of columns: {sorted(widths)}"
+        cols = widths.pop() if widths else 7
     b, m = len(rows), sum(counts)
     ptr = [0]
     for c in counts:
         ptr.append(ptr[-1] + c)
     on_host = all(not r.is_cuda for r in rows) and all(not l.is_cuda for l in labs)
     if on_host:
-        buf = torch.empty((b + 1 + m + 7 * m,), dtype=torch.int32, pin_memory=True)
+        buf = torch.empty((b + 1 + m + cols * m,), dtype=torch.int32, pin_memory=True)
         buf[:b + 1] = torch.tensor(ptr, dtype=torch.int32)
         if m:
             buf[b + 1:b + 1 + m] = torch.cat([l.to(torch.int32) for l in labs])
-            buf[b + 1 + m:].view(torch.float32).view(m, 7).copy_(torch.cat([r[:, :7].float() for r in rows]))
+            buf[b + 1 + m:].view(torch.float32).view(m, cols).copy_(torch.cat([r[:, :cols].float() for r in rows if r.shape[0]]))
         dev = buf.to(device, non_blocking=True)
-        return dev[:b + 1], dev[b + 1 + m:].view(torch.float32).view(m, 7), dev[b + 1:b + 1 + m]
+        return dev[:b + 1], dev[b + 1 + m:].view(torch.float32).view(m, cols), dev[b + 1:b + 1 + m]
     def up(t, dtype):  # (a host tensor in a mixed list goes through pinned memory: a pageable copy would wait)
         return t.to(device=device, dtype=dtype) if t.is_cuda else t.to(dtype).pin_memory().to(device, non_blocking=True)
 
     box_ptr = up(torch.tensor(ptr, dtype=torch.int32), torch.int32)
-    boxes = torch.cat([up(r[:, :7], torch.float32) for r in rows]) if m else torch.empty((0, 7), device=device)
+    boxes = torch.cat([up(r[:, :cols], torch.float32) for r in rows if r.shape[0]]) if m else torch.empty((0, cols), device=device)
     labels = torch.cat([up(l, torch.int32) for l in labs]) if m else torch.empty((0,), dtype=torch.int32, device=device)
     return box_ptr, boxes.contiguous(), labels
 

@@ -4,7 +4,14 @@ get_bboxes :447-608) and `FrustumClusterHead` (frustum_cluster_head.py:19-95, ge
 
 Same constructor arguments, sub-module names (state-dict keys `shared_mlp.*`, `task_heads.N.<attr>.*`) and return
 conventions.  The MLPs are the fused Linear -> LayerNorm+GELU blocks of ops/sst_ops.py; box decoding is the coder of
-core/bbox.py; NMS is the HIP kernel pair K20.  Losses / target assignment (train time) are not built: `loss` raises.
+core/bbox.py; NMS is the HIP kernel pair K20.
+
+Training side: `SparseClusterHeadV2.loss` (sparse_cluster_head_v2.py:170-439 with sparse_cluster_head.py:364-397,459-463) — the
+LiDAR-query head's targets and losses, on the device through K36 (docs/kernels/K36_cluster_losses.md): `fsf_cluster_targets` assigns
+every cluster centre the first GT box of its sample that contains it (K35a's pinned containment test) and encodes the box,
+`fsf_cluster_loss_forward` / `_backward` are the sigmoid focal loss + the L1 groups.  `cluster_targets_host` and
+`loss(..., fused=False)` are the torch restatement the kernels are checked against.  `SparseClusterHead.loss` (v1) and
+`FrustumClusterHead.loss` (another signature, the frustum assigner) are not built and raise.
 """
 from .... import switches
 import copy
@@ -17,12 +24,131 @@ from .... import hip_ops
 from ...core.bbox import BasePointBBoxCoder, LiDARInstance3DBoxes, box3d_multiclass_nms, xywhr2xyxyr
 from ...ops.sst_ops import build_mlp
 from ...registry import BBOX_ASSIGNERS, BBOX_CODERS, HEADS, build_head, build_loss
+from ..decode_heads.segmentation_head import gt_box_rows, pack_gt_for_device, points_in_boxes_first_host
+from ..losses import FocalLoss, L1Loss
 
 
 def _cfg_get(cfg, key, default=None):
     if cfg is None:
         return default
     return cfg.get(key, default)
+
+
+# ----------------------------------------------------------------------------------------------------- K36: targets on the host
+def regroup_gt_for_task(boxes, labels, class_lut, num_task_classes):
+    """`modify_gt_for_single_task_single_sample` with static shapes: the sample's rows regrouped class by class in the order of the
+    task's class names (original order inside a class; a stable sort on the index inside the task), labels replaced by that index.
+    Rows of classes outside the task and rows with label < 0 are keyed last and labelled -1 (every consumer skips them), so nothing
+    here depends on the values: no host wait for device-resident GT.  -> (boxes [M, D], task labels i64 [M])."""
+    labels = labels.reshape(-1).long()
+    lut = class_lut if torch.is_tensor(class_lut) else torch.tensor(class_lut, dtype=torch.long)  # (i64 [num classes], where labels is)
+    known = (labels >= 0) & (labels < lut.numel())
+    key = torch.where(known, lut[labels.clamp(0, lut.numel() - 1)], torch.full_like(labels, -1))
+    key = torch.where(key < 0, torch.full_like(key, num_task_classes), key)
+    key, order = torch.sort(key, stable=True)
+    return boxes[order], torch.where(key < num_task_classes, key, torch.full_like(key, -1))
+
+
+def enlarge_box_rows(boxes7, width):
+    """mmdet3d 0.x `LiDARInstance3DBoxes.enlarged_box`: dims + 2 * width, z_bottom - width."""
+    if not width:
+        return boxes7
+    out = boxes7.clone()
+    out[:, 3:6] += width * 2
+    out[:, 2] -= width
+    return out
+
+
+def encode_box_targets_host(boxes, base_points, code_size):
+    """`BasePointBBoxCoder.encode` with the arithmetic pinned as K36a computes it: the centre delta one f32 subtraction (box columns
+    0..2 as stored), log(f32(dim + 1e-6)) and sin / cos(yaw) in float64 rounded to f32 once (on the CPU whatever the boxes' device),
+    plus box columns 7, 8 when code_size is 10."""
+    boxes = boxes.float()
+    assert boxes.shape[1] in (7, 9, 10) and (boxes.shape[1] == 7) == (code_size == 8), f"bboxes shape: {tuple(boxes.shape)}"
+    dims = (boxes[:, 3:6] + 1e-6).detach().cpu().double().log().float().to(boxes.device)
+    yaw = boxes[:, 6:7].detach().cpu().double()
+    parts = [boxes[:, :3] - base_points.float(), dims, yaw.sin().float().to(boxes.device), yaw.cos().float().to(boxes.device)]
+    if code_size == 10:
+        parts.append(boxes[:, 7:9])
+    return torch.cat(parts, dim=1)
+
+
+def cluster_targets_host(cluster_xyz, batch_idx, gt_rows_list, gt_task_labels_list, num_task_classes, code_size, enlarge_width=None):
+    """`get_targets` / `get_targets_single` / `assign_single` (PseudoSampler, point-in-box assignment) for one task on GT that is
+    already in the task's order: -> (labels i64 [n], label_weights f32 [n], bbox_targets f32 [n, code], bbox_weights f32 [n, code],
+    assigned i64 [n] = index of the box inside its sample's valid rows or -1, stats f32 [6] = (num_preds, num_pos_preds, num_gts,
+    assigned_gts, cls_avg_factor, reg_avg_factor) as totals over the batch).  Rows with label < 0 are dropped first."""
+    xyz = cluster_xyz[:, :3].float()
+    n, dev = xyz.shape[0], xyz.device
+    labels = torch.full((n,), num_task_classes, dtype=torch.long, device=dev)
+    label_weights = xyz.new_ones(n)
+    bbox_targets = xyz.new_zeros((n, code_size))
+    bbox_weights = xyz.new_zeros((n, code_size))
+    assigned = torch.full((n,), -1, dtype=torch.long, device=dev)
+    num_gts = assigned_gts = 0
+    for b, (rows, task_labels) in enumerate(zip(gt_rows_list, gt_task_labels_list)):
+        rows = gt_box_rows(rows).to(dev).float()
+        task_labels = torch.as_tensor(task_labels).to(dev).long().reshape(-1)
+        assert rows.shape[0] == task_labels.shape[0]
+        valid = task_labels >= 0
+        rows, task_labels = rows[valid], task_labels[valid]
+        num_gts += int(rows.shape[0])
+        mine = torch.nonzero(batch_idx == b, as_tuple=False).reshape(-1)
+        if rows.shape[0] == 0 or mine.numel() == 0:
+            continue
+        centres = xyz[mine]
+        inbox = points_in_boxes_first_host(centres, enlarge_box_rows(rows[:, :7], enlarge_width))
+        pos = inbox > -1
+        pos_inds, pos_gt = mine[pos], inbox[pos]
+        assigned[pos_inds] = pos_gt
+        assigned_gts += int(pos_gt.unique().numel())
+        labels[pos_inds] = task_labels[pos_gt]
+        bbox_weights[pos_inds] = 1.0
+        if pos_inds.numel() > 0:
+            pos_rows = rows[pos_gt]
+            bbox_targets[pos_inds] = encode_box_targets_host(pos_rows, centres[pos], code_size)
+            if pos_rows.size(1) == 10:  # zero velocity loss weight for pasted objects
+                assert pos_rows[:, 9].max().item() in (0, 1) and pos_rows[:, 9].min().item() in (0, 1)
+                assert bbox_weights.size(1) == 10, "It is not safe to use -2: as follows if size(1) != 10"
+                bbox_weights[pos_inds, -2:] = pos_rows[:, [9]]
+    assert (labels >= 0).all()
+    num_pos = int((labels < num_task_classes).sum())
+    stats = torch.tensor([n, num_pos, num_gts, assigned_gts, n, num_pos], dtype=torch.float32, device=dev)
+    return labels, label_weights, bbox_targets, bbox_weights, assigned, stats
+
+
+class _ClusterLossFn(torch.autograd.Function):
+    """K36b forward / K36c backward: (loss_cls, loss_center, loss_size, loss_rot, loss_vel) of (cls_logits, reg_preds) with the
+    targets and the averaging factors held fixed.  Head-agnostic: any assigner's labels / targets / weights can feed it."""
+
+    @staticmethod
+    def forward(ctx, cls_logits, reg_preds, labels, label_weights, bbox_targets, bbox_weights, avg_factors, gamma, alpha, loss_weights,
+                with_vel):
+        losses, counts = hip_ops.cluster_loss_forward(cls_logits, reg_preds, labels, label_weights, bbox_targets, bbox_weights, avg_factors,
+                                                      gamma, alpha, loss_weights, with_vel)
+        ctx.save_for_backward(cls_logits, reg_preds, labels, label_weights, bbox_targets, bbox_weights, avg_factors, counts)
+        ctx.cfg = (gamma, alpha, loss_weights, with_vel)
+        ctx.set_materialize_grads(False)
+        return tuple(losses.unbind(0))
+
+    @staticmethod
+    def backward(ctx, *grads):
+        cls_logits, reg_preds, labels, label_weights, bbox_targets, bbox_weights, avg_factors, counts = ctx.saved_tensors
+        grads = [None if g is None else g.float().reshape(1) for g in grads]
+        g_cls, g_reg = hip_ops.cluster_loss_backward(cls_logits, reg_preds, labels, label_weights, bbox_targets, bbox_weights, avg_factors,
+                                                     *ctx.cfg, counts, grads)
+        return (g_cls if ctx.needs_input_grad[0] else None, g_reg if ctx.needs_input_grad[1] else None) + (None,) * 9
+
+
+def _reduce_mean(t):
+    """mmdet `reduce_mean`: the mean over the process group, the tensor itself in a single process."""
+    import torch.distributed as dist
+
+    if not (dist.is_available() and dist.is_initialized()):
+        return t
+    t = t.clone()
+    dist.all_reduce(t.div_(dist.get_world_size()), op=dist.ReduceOp.SUM)
+    return t
 
 
 @HEADS.register_module()
@@ -212,7 +338,7 @@ class SparseClusterHead(nn.Module):
         return full
 
     def loss(self, *args, **kwargs):
-        raise NotImplementedError("head losses / target assignment are train-time code outside the built path")
+        raise NotImplementedError("SparseClusterHead.loss (v1) is not built: the FSF configs use SparseClusterHeadV2, whose loss is")
 
 
 @HEADS.register_module()
@@ -241,6 +367,7 @@ class SparseClusterHeadV2(SparseClusterHead):
             self.task_heads.append(build_head(head_cfg))
         self.class_names = class_names
         self.loss_vel = build_loss(loss_vel) if loss_vel is not None else None
+        self.task_info = {}
 
     def forward(self, feats, pts_xyz=None, pts_inds=None):
         if self.shared_mlp is not None:
@@ -261,6 +388,176 @@ class SparseClusterHeadV2(SparseClusterHead):
         if len(iou_logits_list) > 0:
             outs.update(iou_logits=iou_logits_list)
         return outs
+
+    # ------------------------------------------------------------------------------------------- losses (K36)
+    _REFUSED_TRAIN_CFG = ("max_assign_dist", "assign_by_dist", "code_weight")
+
+    def _check_loss_cfg(self):
+        """Options neither FSF config sets for this head are refused, not approximated."""
+        cfg = self.train_cfg or {}
+        for key in self._REFUSED_TRAIN_CFG:
+            if cfg.get(key, None):
+                raise NotImplementedError(f"SparseClusterHeadV2.loss: train_cfg['{key}'] is not used by the FSF configs and is not built")
+        if self.loss_iou is not None:
+            raise NotImplementedError("SparseClusterHeadV2.loss: loss_iou is not used by the FSF configs and is not built")
+        if self.corner_loss_cfg is not None:
+            raise NotImplementedError("SparseClusterHeadV2.loss: corner_loss_cfg is not used by the FSF configs and is not built")
+        for name in ("loss_cls", "loss_center", "loss_size", "loss_rot", "loss_vel"):
+            mod = getattr(self, name)
+            if getattr(mod, "OUT_OF_SCOPE", False):  # (the Argoverse 2 config's SmoothL1Loss: models/placeholders.py)
+                raise NotImplementedError(f"SparseClusterHeadV2.loss: {name} is a {type(mod).__name__}, which is not built")
+
+    def _fused_loss_ok(self, cls_logits, reg_preds, cluster_xyz):
+        l1 = [self.loss_center, self.loss_size, self.loss_rot] + ([self.loss_vel] if self.loss_vel is not None else [])
+        return (cls_logits.is_cuda and reg_preds.is_cuda and cluster_xyz.is_cuda and cls_logits.dtype == reg_preds.dtype
+                == cluster_xyz.dtype == torch.float32 and cls_logits.dim() == reg_preds.dim() == 2
+                and type(self.loss_cls) is FocalLoss and self.loss_cls.reduction == "mean"
+                and all(type(m) is L1Loss and m.reduction == "mean" for m in l1)
+                and type(self.bbox_coder) is BasePointBBoxCoder and self.box_code_size in (8, 10)
+                and not (self.loss_vel is not None and self.box_code_size != 10))
+
+    def _task_class_lut(self, task_id, device=None):
+        """global class index -> index inside the task, -1 outside it: a list, or with `device` an i64 tensor there, uploaded once
+        (pinned, non-blocking)."""
+        names = self.tasks[task_id]["class_names"]
+        lut = [names.index(n) if n in names else -1 for n in self.class_names]
+        if device is None:
+            return lut
+        cache = self.__dict__.setdefault("_task_luts", {})
+        key = (task_id, str(device), tuple(lut))
+        if key not in cache:
+            host = torch.tensor(lut, dtype=torch.long)
+            cache[key] = host.pin_memory().to(device, non_blocking=True) if torch.device(device).type == "cuda" else host
+        return cache[key]
+
+    def loss(self, cls_logits, reg_preds, cluster_xyz, cluster_inds, gt_bboxes_3d, gt_labels_3d, img_metas=None, iou_logits=None,
+             gt_bboxes_ignore=None, fused=True):
+        """:170-200 — every task's losses and log scalars, keys suffixed with the task's class-name list.  CUDA fp32 inputs with the
+        FocalLoss + L1Loss configuration run K36 (no host wait); `fused=False`, CPU tensors or anything else run the torch restatement
+        with upstream's asserts.  GT: per sample LiDARInstance3DBoxes or [M, 7 | 9 | 10] rows, and labels (rows < 0 are dropped)."""
+        assert isinstance(cls_logits, list) and isinstance(reg_preds, list)
+        assert len(cls_logits) == len(reg_preds) == len(self.tasks)
+        self._check_loss_cfg()
+        all_task_losses = {}
+        self.task_info = {}
+        for i in range(len(self.tasks)):
+            all_task_losses.update(self.loss_single_task(i, cls_logits[i], reg_preds[i], cluster_xyz, cluster_inds, gt_bboxes_3d,
+                                                         gt_labels_3d, iou_logits, fused=fused))
+        return all_task_losses
+
+    def modify_gt_for_single_task(self, gt_bboxes_3d, gt_labels_3d, task_id):
+        """:316-343 — per sample (rows [M', D], task labels i64 [M']) in the task's order.  Host GT loses the rows outside the task, as
+        upstream; device GT keeps them, last and labelled -1, so that no shape depends on device data."""
+        num = len(self.tasks[task_id]["class_names"])
+        out_b, out_l = [], []
+        for gts_b, gts_l in zip(gt_bboxes_3d, gt_labels_3d):
+            rows, labels = gt_box_rows(gts_b), torch.as_tensor(gts_l).reshape(-1)
+            assert rows.size(0) == labels.size(0)
+            if labels.size(0) > 0:
+                rows, labels = regroup_gt_for_task(rows, labels.to(rows.device), self._task_class_lut(task_id, rows.device), num)
+                if not rows.is_cuda:
+                    keep = int((labels >= 0).sum())
+                    rows, labels = rows[:keep], labels[:keep]
+                    if keep > 0:
+                        assert labels.max().item() < num
+            out_b.append(rows)
+            out_l.append(labels.long())
+        return out_b, out_l
+
+    def get_targets(self, num_task_classes, cluster_xyz, batch_idx, gt_bboxes_3d, gt_labels_3d, reg_preds=None, task_id=None, fused=True):
+        """:345-439 — (labels, label_weights, bbox_targets, bbox_weights, iou_labels = None) for GT already in the task's order
+        (`modify_gt_for_single_task`), and `task_info[str(task_id)]` = the four log scalars as f32 device scalars.  They are TOTALS over
+        the batch (upstream overwrites them sample by sample and so reports the last sample's; with one sample the two agree)."""
+        self._check_loss_cfg()
+        width = self.enlarge_width
+        if fused and cluster_xyz.is_cuda and cluster_xyz.dtype == torch.float32:
+            box_ptr, boxes, box_labels = pack_gt_for_device(gt_bboxes_3d, gt_labels_3d, cluster_xyz.device, cols=None)
+            labels, bbox_targets, bbox_weights, assigned, stats = hip_ops.cluster_targets(
+                cluster_xyz, batch_idx, box_ptr, boxes, box_labels, num_task_classes, self.box_code_size, width or 0.0)
+            label_weights = cluster_xyz.new_ones(cluster_xyz.size(0))
+        else:
+            labels, label_weights, bbox_targets, bbox_weights, assigned, stats = cluster_targets_host(
+                cluster_xyz, batch_idx, gt_bboxes_3d, gt_labels_3d, num_task_classes, self.box_code_size, width)
+        self.task_info[str(task_id)] = dict(num_preds=stats[0], num_pos_preds=stats[1], num_gts=stats[2], assigned_gts=stats[3])
+        self._last_assignment = dict(assigned=assigned, avg_factors=stats[4:6])
+        return labels, label_weights, bbox_targets, bbox_weights, None
+
+    def _zero_losses(self, task_id, cls_logits, reg_preds, gt_labels_3d):
+        """No cluster at all: upstream divides 0 by 0; here every loss is 0 with (empty) zero gradients."""
+        zero = cls_logits.sum() * 0 + reg_preds.sum() * 0
+        losses = dict(loss_cls=zero, loss_center=zero, loss_size=zero, loss_rot=zero)
+        dev = reg_preds.device
+        f = lambda v: torch.tensor(float(v), dtype=torch.float32, device=dev)  # noqa: E731
+        num_gts = f(0)
+        for l in gt_labels_3d:  # (device labels are counted where they are)
+            num_gts = num_gts + (l >= 0).sum().to(device=dev, dtype=torch.float32)
+        losses.update(num_preds=f(0), num_pos_preds=f(0), num_gts=num_gts, assigned_gts=f(0))
+        self.task_info[str(task_id)] = {k: losses[k] for k in ("num_preds", "num_pos_preds", "num_gts", "assigned_gts")}
+        if self.loss_vel is not None:
+            losses["loss_vel"] = zero
+        return losses
+
+    def loss_single_task(self, task_id, cls_logits, reg_preds, cluster_xyz, cluster_inds, gt_bboxes_3d, gt_labels_3d, iou_logits=None,
+                         fused=True):
+        """:203-312.  loss_cls = focal over all rows / n; loss_center / loss_size / loss_rot = L1 over the positive rows / num_pos;
+        loss_vel (when the head has it) is called upstream without avg_factor: the plain mean over the positive rows' two columns.
+        Without positives the regression losses are 0 with zero gradients."""
+        self._check_loss_cfg()
+        class_names = self.tasks[task_id]["class_names"]
+        num_task_classes = len(class_names)
+        gt_bboxes_3d, gt_labels_3d = self.modify_gt_for_single_task(gt_bboxes_3d, gt_labels_3d, task_id)
+        batch_idx = cluster_inds if cluster_inds.ndim == 1 else cluster_inds[:, self.BATCH_COL]
+        num_total_samples = len(reg_preds)
+        assert cls_logits.size(0) == num_total_samples == cluster_xyz.size(0) and cls_logits.size(1) == num_task_classes
+        assert reg_preds.size(1) == self.box_code_size
+        if num_total_samples == 0:
+            losses = self._zero_losses(task_id, cls_logits, reg_preds, gt_labels_3d)
+            return {k + f"{class_names}": v for k, v in losses.items()}
+        use_kernels = fused and self._fused_loss_ok(cls_logits, reg_preds, cluster_xyz)
+        if not use_kernels:
+            cls_logits, reg_preds, cluster_xyz = cls_logits.float(), reg_preds.float(), cluster_xyz.float()
+        labels, label_weights, bbox_targets, bbox_weights, _ = self.get_targets(
+            num_task_classes, cluster_xyz, batch_idx, gt_bboxes_3d, gt_labels_3d, reg_preds, task_id, fused=use_kernels)
+        avg_factors = self._last_assignment["avg_factors"]  # (cls, reg) = (n, num_pos) as f32 scalars where the targets live
+        sync = (self.sync_cls_avg_factor, self.sync_reg_avg_factor)
+        if any(sync):
+            synced = _reduce_mean(avg_factors)
+            if synced is not avg_factors:  # (a process group exists: the all-reduce sits between targets and losses on the stream)
+                avg_factors = torch.stack([synced[k] if sync[k] else avg_factors[k] for k in range(2)])
+        if use_kernels:
+            with_vel = self.loss_vel is not None
+            weights = (self.loss_cls.loss_weight, self.loss_center.loss_weight, self.loss_size.loss_weight, self.loss_rot.loss_weight,
+                       self.loss_vel.loss_weight if with_vel else 0.0)
+            out = _ClusterLossFn.apply(cls_logits, reg_preds, labels, None, bbox_targets, bbox_weights, avg_factors,
+                                       float(self.loss_cls.gamma), float(self.loss_cls.alpha), tuple(float(w) for w in weights), with_vel)
+            losses = dict(loss_cls=out[0], loss_center=out[1], loss_size=out[2], loss_rot=out[3])
+            losses.update(self.task_info[str(task_id)])
+            if with_vel:
+                losses["loss_vel"] = out[4]
+            return {k + f"{class_names}": v for k, v in losses.items()}
+        assert (label_weights == 1).all(), "for now"
+        cls_avg_factor, reg_avg_factor = avg_factors[0], avg_factors[1]
+        loss_cls = self.loss_cls(cls_logits, labels, label_weights, avg_factor=cls_avg_factor)
+        pos_inds = ((labels >= 0) & (labels < num_task_classes)).nonzero(as_tuple=False).reshape(-1)
+        num_pos = len(pos_inds)
+        pos_reg_preds, pos_bbox_targets, pos_bbox_weights = reg_preds[pos_inds], bbox_targets[pos_inds], bbox_weights[pos_inds]
+        if num_pos > 0:
+            loss_center = self.loss_center(pos_reg_preds[:, :3], pos_bbox_targets[:, :3], pos_bbox_weights[:, :3], avg_factor=reg_avg_factor)
+            loss_size = self.loss_size(pos_reg_preds[:, 3:6], pos_bbox_targets[:, 3:6], pos_bbox_weights[:, 3:6], avg_factor=reg_avg_factor)
+            loss_rot = self.loss_rot(pos_reg_preds[:, 6:8], pos_bbox_targets[:, 6:8], pos_bbox_weights[:, 6:8], avg_factor=reg_avg_factor)
+            if self.loss_vel is not None:
+                loss_vel = self.loss_vel(pos_reg_preds[:, 8:10], pos_bbox_targets[:, 8:10], pos_bbox_weights[:, 8:10])
+        else:
+            loss_center = pos_reg_preds.sum() * 0
+            loss_size = pos_reg_preds.sum() * 0
+            loss_rot = pos_reg_preds.sum() * 0
+            if self.loss_vel is not None:
+                loss_vel = pos_reg_preds.sum() * 0
+        losses = dict(loss_cls=loss_cls, loss_center=loss_center, loss_size=loss_size, loss_rot=loss_rot)
+        losses.update(self.task_info[str(task_id)])
+        if self.loss_vel is not None:
+            losses["loss_vel"] = loss_vel
+        return {k + f"{class_names}": v for k, v in losses.items()}
 
     # ------------------------------------------------------------------------------------------- boxes
     @torch.no_grad()
@@ -412,6 +709,10 @@ class FrustumClusterHead(SparseClusterHeadV2):
         self.task_info = {}
         self.vis_dir = vis_dir
         self.use_one_to_one = use_one_to_one
+
+    def loss(self, *args, **kwargs):
+        raise NotImplementedError("FrustumClusterHead.loss (frustum_cluster_head.py:138-265: FrustumAssigner, 2-D IoU + 3-D) is not built; "
+                                  "only the LiDAR-query head (SparseClusterHeadV2.loss) has targets and losses")
 
     @torch.no_grad()
     def get_bboxes(self, cls_logits, reg_preds, preds_2d, cluster_xyz, cluster_inds, input_metas, iou_logits=None,

@@ -1000,17 +1000,22 @@ class FSF(SingleStageFSD):
             stages.append((obj_centers, obj_result, res_query_feat))
         return stages
 
-    def forward_train_graph(self, points, img_metas, mask_data, mask_anno, gt_bboxes_3d=None, gt_labels_3d=None):
+    def forward_train_graph(self, points, img_metas, mask_data, mask_anno, gt_bboxes_3d=None, gt_labels_3d=None,
+                            lidar_head_losses=False):
         """The differentiable graph of `forward_train` (:806-903) — segmentor + image fusion + segmentation head, camera queries
         WITH `frustum_obj_head`, LiDAR queries WITH `bbox_head`, `combine_frustum_and_fsd` (both `combine_*_mlp`), and
         `multi_stage_refine_train` (:905-959: RoI point pooling, `refine_sir_layers`, `lidar_img_mlp`, `position_encoder`,
-        `out_proj`, `frustum_refined_head`) — up to the tensors the losses would consume.  Target assignment and the losses themselves
-        (`*.loss(...)`: host-side label bookkeeping) are out of scope; the caller supplies a scalar of these
-        outputs (bench.py::dummy_loss: their sum, SURVEY §8(d) config 3).
+        `out_proj`, `frustum_refined_head`) — up to the tensors the losses would consume.  The camera head's and the refine stages'
+        target assignment and losses (`*.loss(...)`) are not built; a caller without them supplies a scalar
+        of these outputs (bench.py::dummy_loss: their sum, SURVEY §8(d) config 3).
 
         With `gt_bboxes_3d` / `gt_labels_3d` (per sample: LiDARInstance3DBoxes or [M, >=7] tensors, and labels) the segmentation
         head's losses (`segmentor_feat_inhance_train`, :730-770) are added as out["losses"] = dict(loss_sem_seg, loss_vote), on the
-        device with no host wait (K35).  Without them the call and its output are unchanged."""
+        device with no host wait (K35).  Without them the call and its output are unchanged.
+
+        `lidar_head_losses=True` (needs the GT) also adds the LiDAR-query head's losses and log scalars, `bbox_head.loss(...)` on
+        `fsd_obj_result` / `fsd_obj_centers` / `fsd_obj_coors` (:862-868), under their upstream keys `fsd_<name><class names>`, on the
+        device with no host wait (K36).  Without the flag out["losses"] has the two segmentation keys only."""
         self._gather_cache = None
         self._fg_cache = None
         self._img_pre = None
@@ -1031,6 +1036,12 @@ class FSF(SingleStageFSD):
             labels, vote_targets, vote_mask = head.get_targets_flat(seg_out_dict["seg_points"], seg_out_dict["batch_idx"],
                                                                     gt_bboxes_3d, gt_labels_3d)
             seg_losses = head.losses(seg_out_dict["seg_logits"], seg_out_dict["seg_vote_preds"], labels, vote_targets, vote_mask)
+            if lidar_head_losses:
+                fsd_losses = self.bbox_head.loss(l_result["cls_logits"], l_result["reg_preds"], l_centers, l_coors, gt_bboxes_3d,
+                                                 gt_labels_3d, img_metas, iou_logits=l_result.get("iou_logits", None))
+                seg_losses.update({"fsd_" + k: v for k, v in fsd_losses.items()})
+        elif lidar_head_losses:
+            raise ValueError("forward_train_graph(lidar_head_losses=True) needs gt_bboxes_3d and gt_labels_3d")
         out = dict(seg=seg_out_dict, frustum_obj_feats=f_feats, frustum_obj_centers=f_centers, frustum_obj_coors=f_coors,
                    frustum_preds_2d=f_preds_2d, frustum_obj_result=f_result, fsd_obj_feats=l_feats, fsd_obj_centers=l_centers,
                    fsd_obj_coors=l_coors, fsd_obj_result=l_result, stage_results=[])
@@ -1050,10 +1061,12 @@ class FSF(SingleStageFSD):
         return out
 
     def forward_train(self, points, img_metas, *args, mask_data=None, mask_anno=None, **kwargs):
-        """`forward_train` (:806-903): the graph is `forward_train_graph`; the `.loss(...)` calls that close it upstream (label
-        assignment on the host, focal / L1 losses) are outside the built path and the heads' `loss` says so."""
+        """`forward_train` (:806-903): the graph is `forward_train_graph`, which also closes the segmentation head (K35) and the
+        LiDAR-query head (K36) with their losses; the camera head's and the refine stages' `.loss(...)` (FrustumAssigner, distance
+        assigner) are not built, so the whole training step is not either."""
         # (ADVICE r5: this used to run the whole graph and only then raise through `head.loss`)
         raise NotImplementedError(
-            "FSF.forward_train: target assignment and the losses (`*.loss(...)`, FSF.py:806-903) are host-side code outside the built "
-            "path; `forward_train_graph(points, img_metas, mask_data, mask_anno)` returns every tensor they would consume, and with "
-            "`gt_bboxes_3d=..., gt_labels_3d=...` also the segmentation head's losses (out['losses'])")
+            "FSF.forward_train: the camera-query head's and the refine stages' target assignment and losses (`frustum_obj_head.loss`, "
+            "`frustum_refined_head.loss`, FSF.py:806-903) are not built; `forward_train_graph(points, img_metas, mask_data, mask_anno)` "
+            "returns every tensor they would consume, with `gt_bboxes_3d=..., gt_labels_3d=...` also the segmentation head's losses and "
+            "with `lidar_head_losses=True` the LiDAR-query head's (out['losses'])")

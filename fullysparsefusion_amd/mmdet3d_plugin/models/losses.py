@@ -1,7 +1,7 @@
-"""`CrossEntropyLoss` and `L1Loss` (LOSSES) in the semantics of the mmdet 2.14 pin (mmdet/models/losses/cross_entropy_loss.py,
-smooth_l1_loss.py, utils.py::weight_reduce_loss).  Plain torch: the segmentation head's fused device path (K35, VoteSegHead.losses)
-reads `class_weight` / `loss_weight` from these modules and never calls them.  They hold no parameters or buffers (`class_weight`
-is a plain attribute), so building them changes no state_dict."""
+"""`CrossEntropyLoss`, `L1Loss` and `FocalLoss` (LOSSES) in the semantics of the mmdet 2.14 pin (mmdet/models/losses/
+cross_entropy_loss.py, smooth_l1_loss.py, focal_loss.py, utils.py::weight_reduce_loss).  Plain torch: the fused device paths (K35,
+VoteSegHead.losses; K36, SparseClusterHeadV2.loss) read `class_weight` / `gamma` / `alpha` / `loss_weight` from these modules and never
+call them.  They hold no parameters or buffers (`class_weight` is a plain attribute), so building them changes no state_dict."""
 import torch
 import torch.nn.functional as F
 from torch import nn
@@ -99,3 +99,41 @@ class L1Loss(nn.Module):
         assert reduction_override in (None, "none", "mean", "sum")
         reduction = reduction_override if reduction_override else self.reduction
         return self.loss_weight * l1_loss(pred, target, weight, reduction=reduction, avg_factor=avg_factor)
+
+
+def sigmoid_focal_loss(pred, target, weight=None, gamma=2.0, alpha=0.25, reduction="mean", avg_factor=None):
+    """mmdet 2.14 `py_sigmoid_focal_loss` on integer labels: pred [N, C] logits, target i64 [N] with C = background (its one-hot row
+    is all zero).  FL = -alpha t (1 - p)^gamma log p - (1 - alpha)(1 - t) p^gamma log(1 - p), p = sigmoid(pred); the log terms come
+    from binary_cross_entropy_with_logits, so large |pred| gives neither inf nor log 0.  `weight` [N] applies to every class of a row."""
+    num_classes = pred.size(1)
+    target = F.one_hot(target, num_classes=num_classes + 1)[:, :num_classes].type_as(pred)
+    pred_sigmoid = pred.sigmoid()
+    pt = (1 - pred_sigmoid) * target + pred_sigmoid * (1 - target)
+    focal_weight = (alpha * target + (1 - alpha) * (1 - target)) * pt.pow(gamma)
+    loss = F.binary_cross_entropy_with_logits(pred, target, reduction="none") * focal_weight
+    if weight is not None:
+        if weight.shape != loss.shape:
+            if weight.size(0) == loss.size(0):
+                weight = weight.view(-1, 1)
+            else:
+                assert weight.numel() == loss.numel()
+                weight = weight.view(loss.size(0), -1)
+        assert weight.ndim == loss.ndim
+    return weight_reduce_loss(loss, weight, reduction, avg_factor)
+
+
+@LOSSES.register_module()
+class FocalLoss(nn.Module):
+    def __init__(self, use_sigmoid=True, gamma=2.0, alpha=0.25, reduction="mean", loss_weight=1.0):
+        super().__init__()
+        assert use_sigmoid is True, "Only sigmoid focal loss supported now."
+        self.use_sigmoid = use_sigmoid
+        self.gamma, self.alpha = gamma, alpha
+        self.reduction = reduction
+        self.loss_weight = loss_weight
+
+    def forward(self, pred, target, weight=None, avg_factor=None, reduction_override=None):
+        assert reduction_override in (None, "none", "mean", "sum")
+        reduction = reduction_override if reduction_override else self.reduction
+        return self.loss_weight * sigmoid_focal_loss(pred, target, weight, gamma=self.gamma, alpha=self.alpha, reduction=reduction,
+                                                     avg_factor=avg_factor)

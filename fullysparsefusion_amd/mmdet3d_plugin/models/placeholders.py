@@ -23,7 +23,7 @@ def out_of_scope(name, where, module=False):
 
 for _reg, _where, _module, _names in (
         (MODELS, "heads / losses of the training path", True,
-         "MultiStageRefineHead GroupCorrectionHead FocalLoss SmoothL1Loss"),
+         "MultiStageRefineHead GroupCorrectionHead SmoothL1Loss"),
         (BBOX_CODERS, "core/bbox/coders", False, "ABSPointBBoxCoder"),
         (BBOX_ASSIGNERS, "core/bbox/assigners", False, "HybridAssigner FrustumAssigner PointInBoxAssigner DistAssigner MaxIoUAssigner"),
         (PIPELINES, "datasets/pipelines (training augmentations)", False,

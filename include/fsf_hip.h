@@ -502,6 +502,58 @@ int fsf_seg_loss_backward(const float* logits, int64_t ld_logits, const float* v
                           float* grad_votes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * K36  query-head (cluster head) targets and losses (docs/kernels/K36_cluster_losses.md)
+ * Replaces SparseClusterHeadV2.get_targets / get_targets_single / loss_single_task with SparseClusterHead.assign_single,
+ *   BasePointBBoxCoder.encode, mmdet3d's PseudoSampler and mmdet 2.14 FocalLoss(use_sigmoid) + L1Loss
+ *   (projects/mmdet3d_plugin/models/dense_heads/sparse_cluster_head_v2.py:203-439).  Nothing here synchronises; no float atomics.
+ * K36a fsf_cluster_targets: 3 launches (per-box constants, one lane per cluster, final counts).
+ *   cluster_xyz f32 rows of xyz_stride (>= 3) floats; batch_idx i32 (batch_idx_bytes 4) or i64 (8), element i at batch_idx[i * batch_stride]
+ *               (a column of the [n, 3] cluster index table is passed as it lies)
+ *   box_ptr     i32 [num_samples + 1] device: CSR of sample b's rows of boxes / box_labels, ALREADY in the task's order (class by class)
+ *   boxes       f32 rows of box_stride floats, box_cols (7 | 9 | 10) of them used: (x, y, z_bottom, w, l, h, yaw[, vx, vy[, flag]]);
+ *               box_labels i32 [num_boxes]: label inside the task, rows < 0 are skipped.  box_cols = 7 needs code_size 8, else 10
+ *   labels      i64 [n]: task label of the FIRST box of the cluster's sample that contains the centre (K35a's containment test on the
+ *               box enlarged by enlarge_width: dims + 2e, z_bottom - e), num_classes when none
+ *   bbox_targets f32 [n, code_size]: (box xyz - centre, log(dims + 1e-6), sin yaw, cos yaw[, box columns 7, 8]) on positives, else 0.
+ *               log / sin / cos are float64 functions of the f32 value (dim + 1e-6f in f32), rounded to f32 once
+ *   bbox_weights f32 [n, code_size]: 1 on positives (columns 8, 9 = box column 9 when box_cols = 10), else 0
+ *   assigned    i32 [n]: index of that box inside its sample, -1 when none
+ *   stats       f32 [6] device: (num_preds, num_pos_preds, num_gts, assigned_gts, cls_avg_factor = n, reg_avg_factor = num_pos),
+ *               totals over the batch.  n, num_boxes < 2^24.  workspace: fsf_cluster_targets_workspace_bytes(num_boxes, n)
+ * K36b fsf_cluster_loss_forward: 2 launches.  cls_logits f32 [n, C] (row stride ld_cls), reg_preds f32 [n, code_size] (ld_reg), labels
+ *   i64 [n] (a row is positive when 0 <= label < C), label_weights f32 [n] or NULL (= 1), bbox_targets / bbox_weights f32 [n, code_size],
+ *   avg_factors f32 [2] device (cls, reg) -> losses f32 [5] device:
+ *   [0] w_cls * sum_{i,c} lw_i FL(z_ic, [label_i == c]) / avg_factors[0],
+ *       FL = -alpha t (1 - p)^gamma log p - (1 - alpha)(1 - t) p^gamma log(1 - p), p = sigmoid(z), in softplus form in fp64
+ *   [1..3] w_center / w_size / w_rot * sum over positive rows of |pred - target| * weight on columns 0..2 / 3..5 / 6..7 / avg_factors[1]
+ *   [4] w_vel * mean over positive rows of |pred - target| * weight on columns 8..9 (with_vel != 0 needs code_size 10; else 0)
+ *   [1..4] are 0 when no row is positive.  counts i64 [1] = positive rows, for the backward.  fp64 terms, per-workgroup partials, one
+ *   final workgroup.  workspace: fsf_cluster_loss_workspace_bytes(n)
+ * K36c fsf_cluster_loss_backward: 1 launch.  grad_*_loss f32 [1] device or NULL (= 0): upstream gradients of the five losses ->
+ *   grad_cls_logits f32 [n, C] and grad_reg_preds f32 [n, code_size], dense, every element written once; sign(0) = 0; the sigmoid is
+ *   recomputed.
+ */
+int64_t fsf_cluster_targets_workspace_bytes(int64_t num_boxes, int64_t n);
+int fsf_cluster_targets(const float* cluster_xyz, int64_t n, int64_t xyz_stride, const void* batch_idx, int32_t batch_idx_bytes,
+                        int64_t batch_stride, const int32_t* box_ptr, int32_t num_samples, const float* boxes, int64_t num_boxes,
+                        int64_t box_stride, int32_t box_cols, const int32_t* box_labels, int32_t num_classes, int32_t code_size,
+                        float enlarge_width, void* workspace, int64_t workspace_bytes, int64_t* labels, float* bbox_targets,
+                        float* bbox_weights, int32_t* assigned, float* stats, void* stream);
+int64_t fsf_cluster_loss_workspace_bytes(int64_t n);
+int fsf_cluster_loss_forward(const float* cls_logits, int64_t ld_cls, const float* reg_preds, int64_t ld_reg, int64_t n,
+                             int32_t num_classes, int32_t code_size, const int64_t* labels, const float* label_weights,
+                             const float* bbox_targets, const float* bbox_weights, const float* avg_factors, float gamma, float alpha,
+                             float w_cls, float w_center, float w_size, float w_rot, float w_vel, int32_t with_vel, void* workspace,
+                             int64_t workspace_bytes, float* losses, int64_t* counts, void* stream);
+int fsf_cluster_loss_backward(const float* cls_logits, int64_t ld_cls, const float* reg_preds, int64_t ld_reg, int64_t n,
+                              int32_t num_classes, int32_t code_size, const int64_t* labels, const float* label_weights,
+                              const float* bbox_targets, const float* bbox_weights, const float* avg_factors, float gamma, float alpha,
+                              float w_cls, float w_center, float w_size, float w_rot, float w_vel, int32_t with_vel,
+                              const int64_t* counts, const float* grad_cls_loss, const float* grad_center_loss,
+                              const float* grad_size_loss, const float* grad_rot_loss, const float* grad_vel_loss,
+                              float* grad_cls_logits, float* grad_reg_preds, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * K13-K15  LiDAR -> camera projection + per-point instance-mask gather
  * Replaces: FSF.prj_points_2d (projects/mmdet3d_plugin/models/detectors/FSF.py:169-200) and
  *   FSF.points_in_mask (:202-226) for one batch sample; the caller loops samples like frustum_gather (:228-258).
