@@ -697,6 +697,10 @@ class FSF(SingleStageFSD):
 
     def _segment(self, points, img_metas, mask_data, mask_anno):
         """Stage 1 (:1114-1126): the segmentor's features with the image branch mixed in; returns (seg_out_dict, point_infos)."""
+        for b, p in enumerate(points):
+            if p.shape[0] == 0:
+                # (the reference raises too, on `batch_idx.max()` of an empty tensor in group_sample: single_stage_fsd.py:803-804)
+                raise ValueError(f"FSF: sample {b} of the batch has no points; a frame whose range filter leaves nothing cannot be detected on")
         if self.voxel_downsampling_size is not None:
             points = self.segmentor.voxel_downsample(points)
         front = self._take_front(points, img_metas, mask_data, mask_anno)
@@ -851,7 +855,8 @@ class FSF(SingleStageFSD):
 
     def query_feat_refine(self, points, pts_feat, batch_idx, input_bbox_rois, i_stage, point_infos, mask_anno, mask_data,
                           img_metas):
-        ext_pts_inds, ext_pts_roi_inds, ext_pts_info = self.roi_extractor(points[:, :3], batch_idx, input_bbox_rois[:, :8])
+        ext_pts_inds, ext_pts_roi_inds, ext_pts_info = self.roi_extractor(points[:, :3], batch_idx, input_bbox_rois[:, :8],
+                                                                          batch_size=len(img_metas) if img_metas is not None else None)
         info13 = ext_pts_info.get("_fsf_info13")
         if (info13 is not None and not torch.is_grad_enabled() and points.is_cuda and points.dtype == torch.float32
                 and input_bbox_rois.dtype == torch.float32 and getattr(ext_pts_roi_inds, "_fsf_real_rows", False)):

@@ -24,25 +24,33 @@ class DynamicPointROIExtractor(nn.Module):
         self.max_inbox_point = max_inbox_point
         self.max_all_pts = max_all_pts  # upstream: the default of DynamicPointPoolFunction.forward, PER SAMPLE
 
-    def forward(self, pts_xyz, batch_inds, rois):
+    def forward(self, pts_xyz, batch_inds, rois, batch_size=None):
         """pts_xyz [P,3], batch_inds [P] (sorted), rois [R,8] (batch, x, y, z_bottom, w, l, h, rz) ->
-        (point indices [k], roi indices [k], dict(local_xyz [k,3], boundary_offset [k,6], is_in_margin [k]))."""
+        (point indices [k], roi indices [k], dict(local_xyz [k,3], boundary_offset [k,6], is_in_margin [k])).
+        `batch_size`: the number of samples where the caller knows it on the host (FSF does); read from `batch_inds` otherwise."""
         assert len(pts_xyz) > 0 and len(batch_inds) > 0 and len(rois) > 0
         rois = rois.float()
         if rois.size(1) == 7:  # one sample: the reference's op itself (ops/dynamic_point_pool_op.py), fake row included
             inds, roi_inds, info = dynamic_point_pool(rois, pts_xyz.float(), self.extra_wlh, self.max_inbox_point,
                                                       self.max_all_pts)
-        else:  # the per-sample loop of :44-73 as ONE launch: the batch index travels into the kernel
-            inds, roi_inds, info = hip_ops.dynamic_point_pool(
-                rois, pts_xyz.float(), self.extra_wlh, self.max_inbox_point, self.max_all_pts,
-                roi_batch_col=0, box_col=1, pts_batch=batch_inds)
+        else:
+            if batch_size is None:
+                batch_size = int(batch_inds[-1]) + 1  # (sorted)
+            if batch_size == 1:  # the per-sample loop of :44-73 as ONE launch: the batch index travels into the kernel
+                inds, roi_inds, info = hip_ops.dynamic_point_pool(
+                    rois, pts_xyz.float(), self.extra_wlh, self.max_inbox_point, self.max_all_pts,
+                    roi_batch_col=0, box_col=1, pts_batch=batch_inds)
+            else:
+                inds, roi_inds, info = self._pool_per_sample(pts_xyz.float(), batch_inds, rois, batch_size)
             real = inds.numel() > 0
             if not real:  # upstream fakes one (-1, -1, zeros) row so that downstream shapes stay non-empty
-                inds = inds.new_full((1,), -1)
+                # (the point index -1 is only ever used to READ a row, the last one; it is spelled out, because the native gathers
+                # take indices as they are and -1 would read in front of the buffer.  The RoI index stays -1: the head drops that group)
+                inds = inds.new_full((1,), len(pts_xyz) - 1)
                 roi_inds = roi_inds.new_full((1,), -1)
                 info = info.new_zeros((1, 13))
             roi_inds._fsf_real_rows = real  # (known on the host: every roi index is then >= 0)
-        if self.debug and inds[0] >= 0:
+        if self.debug and roi_inds[0] >= 0:
             roi_per_pts = rois[:, -7:][roi_inds]
             assert torch.isclose(pts_xyz[inds], info[:, :3]).all()
             assert torch.isclose(info[:, 6] + info[:, 9], roi_per_pts[:, 4], atol=1e-4).all()
@@ -53,6 +61,28 @@ class DynamicPointROIExtractor(nn.Module):
             ext_pts_info["_fsf_info13"] = info  # (the three views' one tensor: FSF.query_feat_refine hands it to K29e)
         roi_inds._fsf_sorted = True  # K17's rows come in ascending (roi, point) order: FullySparseBboxHead's groups are contiguous runs
         return inds, roi_inds, ext_pts_info
+
+    def _pool_per_sample(self, pts_xyz, batch_inds, rois, batch_size):
+        """A batch: one pooling call per sample (:44-73), because `max_all_pts` is the op's output capacity PER CALL, i.e. per sample
+        (ops/dynamic_point_pool_op.py:27-29) — one launch over the batch would share one capacity between the samples, in RoI order,
+        and the samples' RoIs interleave (camera queries, then LiDAR queries group by group).  Rows come back in ascending (RoI, point)
+        order over the whole batch, as the one launch returns them."""
+        counts = torch.bincount(batch_inds, minlength=batch_size).tolist()
+        roi_batch = rois[:, 0].long()
+        parts, start = [], 0
+        for b in range(batch_size):
+            r_idx = (roi_batch == b).nonzero(as_tuple=False).squeeze(1)
+            if counts[b] > 0 and r_idx.numel() > 0:
+                i, r, f = hip_ops.dynamic_point_pool(rois.index_select(0, r_idx)[:, 1:].contiguous(), pts_xyz[start:start + counts[b]],
+                                                     self.extra_wlh, self.max_inbox_point, self.max_all_pts)
+                if i.numel() > 0:
+                    parts.append((i + start, r_idx.index_select(0, r), f))
+            start += counts[b]
+        if not parts:
+            return (batch_inds.new_zeros((0,)), batch_inds.new_zeros((0,)), pts_xyz.new_zeros((0, 13)))
+        inds, roi_inds, info = (torch.cat([p[k] for p in parts]) for k in range(3))
+        order = torch.argsort(roi_inds, stable=True)  # (a RoI's rows all come from one sample, in ascending point order already)
+        return inds.index_select(0, order), roi_inds.index_select(0, order), info.index_select(0, order)
 
 
 @HEADS.register_module()

@@ -275,18 +275,33 @@ def double_overlap_pts(pts_feat, bz_coor, points, obj_id_tensor, w):
     return torch.cat(feats), torch.cat(bzs), torch.cat(pts), torch.cat(ids), torch.cat(ws)
 
 
-def fsf_stage2(fsf, s1, mask_anno, img_hw):
-    """FSF.frustum_forward without the head (FSF.py:607-650)."""
+def fsf_stage2(fsf, s1, mask_anno, img_hw, fake_if_empty=True):
+    """FSF.frustum_forward without the head (FSF.py:607-650).
+
+    No point inside any mask (`obj_id_tensor.sum() == 0` after `extract_fg_pts`, FSF.py:400-414): the reference fakes ONE object —
+    one all-zero point with all-zero features, key (0, 0, 0), zero offset, zero centre — and runs the SIR stack on it, so the
+    frame has exactly one camera query, with id 0 (-> the all-zero 2-D prediction row with category = num_classes, :506-535).
+    That test is over everything `frustum_pooling` is handed, i.e. over the whole BATCH: a sample without camera points inside a
+    batch that has some gets no fake object and no camera query at all.  `fake_if_empty=False` is that case (simple_test_batch):
+    every output comes back with zero rows."""
     w = 1 - s1["seg_logits"].softmax(1)[:, -1]
     obj = s1["obj_id"]
     fg = obj.sum((-2, -1)) > 0
-    a = (s1["seg_feats"][fg], s1["batch_idx"][fg].unsqueeze(-1), s1["seg_points"][fg], obj[fg], w[fg])
-    feat, bz, pts, ids, ww = double_overlap_pts(*a)
-    sir_coors = torch.cat([bz, torch.zeros_like(bz), ids.unsqueeze(-1)], dim=-1)
-    pw = ww.unsqueeze(-1).clamp(min=1e-5)
-    mean, mcoors, inv = oscatter.scatter_v2(torch.cat([pts[:, :3] * pw, pw], -1), sir_coors, "avg")
-    center = mean[:, :3] / mean[:, 3:4]
-    f_cluster = pts[:, :3] - center[inv]
+    empty = int(fg.sum()) == 0
+    if empty:  # FSF.py:407-414
+        feat = s1["seg_feats"].new_zeros((1, s1["seg_feats"].shape[1]))
+        pts = s1["seg_points"].new_zeros((1, s1["seg_points"].shape[1]))
+        sir_coors = s1["batch_idx"].new_zeros((1, 3))
+        f_cluster = pts.new_zeros((1, 3))
+        center = pts.new_zeros((1, 3))
+    else:
+        a = (s1["seg_feats"][fg], s1["batch_idx"][fg].unsqueeze(-1), s1["seg_points"][fg], obj[fg], w[fg])
+        feat, bz, pts, ids, ww = double_overlap_pts(*a)
+        sir_coors = torch.cat([bz, torch.zeros_like(bz), ids.unsqueeze(-1)], dim=-1)
+        pw = ww.unsqueeze(-1).clamp(min=1e-5)
+        mean, mcoors, inv = oscatter.scatter_v2(torch.cat([pts[:, :3] * pw, pw], -1), sir_coors, "avg")
+        center = mean[:, :3] / mean[:, 3:4]
+        f_cluster = pts[:, :3] - center[inv]
     _, cluster_feats, out_coors = sir_forward(fsf.frustum_sir, pts, feat, sir_coors, f_cluster)
     ids_k = out_coors[:, 2]
     preds = torch.zeros((out_coors.size(0), 9), dtype=feat.dtype)  # (float64 when the chain runs in float64: test arbitration)
@@ -298,8 +313,12 @@ def fsf_stage2(fsf, s1, mask_anno, img_hw):
     bbox[:, 1::2] /= img_hw[0]
     enc = torch.cat([bbox, preds[:, 4:5], F.one_hot(preds[:, 5].long(), fsf.num_classes + 1).to(feat.dtype)], -1)
     img_feat = apply_module(fsf.encode_2d_mlp, enc)
-    return dict(obj_feat=torch.cat([cluster_feats, img_feat], -1), obj_coors=out_coors, obj_centers=center,
-                sir_coors=sir_coors, f_cluster=f_cluster, preds_2d=preds)
+    out = dict(obj_feat=torch.cat([cluster_feats, img_feat], -1), obj_coors=out_coors, obj_centers=center,
+               sir_coors=sir_coors, f_cluster=f_cluster, preds_2d=preds)
+    if empty and not fake_if_empty:  # (the widths come from the evaluation above, the rows are dropped)
+        out = {k: v[:0] for k, v in out.items()}
+    out["fake"] = bool(empty and fake_if_empty)
+    return out
 
 
 def connected_components_xy(points, dist):
@@ -331,76 +350,157 @@ def connected_components_xy(points, dist):
 
 
 def fsf_stage3(fsf, s1, record=None, replay=None):
-    """FSF.fsd_forward without the head (FSF.py:569-600): pre_voxelize, group_sample, ClusterAssigner, SIR.
+    """FSF.fsd_forward without the head (FSF.py:569-600): pre_voxelize, group_sample, ClusterAssigner, SIR — one sample.
 
     `record` (a dict) receives every INTEGER / boolean decision of the stage — the pre-voxelization cells, per class group the
     foreground mask, the arg-max tie weights of the vote, the density-filter mask, the cluster-voxel map and the component labels.
     `replay` (such a dict) takes them from there instead of deriving them: the float64 arbitration chain of
     tests/test_e2e_agreement_gpu.py runs the stage's ARITHMETIC in float64 on the integer structure the fp32 chain decided (a float64
     threshold test or floor would move a handful of borderline points between cells / clusters and the two chains would no longer
-    describe the same groups)."""
+    describe the same groups).
+
+    Empty intermediates (single_stage_fsd.py): a group without a pre-voxel above its score threshold gets the sample's first
+    pre-voxel (:832-834, `get_sample_beg_position`); a group none of whose voted centres lies in a cell with `min_points` centres
+    keeps all of them (`valid_mask = ~valid_mask`, :952-954).  One sample therefore always has at least one LiDAR query per class
+    group; the batch forms of both rules are in `fsf_stage3_batch`."""
+    return _fsf_stage3(fsf, [s1], record, replay)[0]
+
+
+def fsf_stage3_batch(fsf, s1_list):
+    """`fsf_stage3` for a batch (`s1_list[b]["batch_idx"]` holds b): per sample the dict `fsf_stage3` returns.  A sample's result is
+    its single-sample result except for three rules that the reference states over the whole batch (single_stage_fsd.py):
+
+    * :832-834 — when ANY sample has no pre-voxel above a group's threshold (`len(unique(batch_idx[fg_mask])) < bsz`), the first
+      pre-voxel of EVERY sample becomes foreground for that group (`get_sample_beg_position`: one position per sample), also in
+      the samples that have foreground of their own;
+    * :952-954 — `valid_mask.any()` is taken over the group's centres of all samples: the mask is inverted only when NO sample has
+      a dense cell, and then for every sample.  A sample whose centres are all sparse, next to a sample with a dense cell, keeps
+      none: it can end with no LiDAR query in that group, or in any group;
+    * :69-82, :977 — test-time clustering (`find_connected_componets_single_batch`) ignores the sample index: components are taken
+      over the cell centroids of ALL samples (rows in the order of the (sample, x, y, z) unique, :962), and a cluster is the pair
+      (sample, component) (:981).  Two clusters of one sample merge when centroids of another sample bridge them.  The ids are
+      the batch-wide component labels; they are defined up to renumbering (compare them as partitions).
+
+    Everything else of the stage is row-wise or grouped by a key that carries the sample index, so it is evaluated per sample
+    (bit-identical to the single-sample call when none of the three rules fires)."""
+    return _fsf_stage3(fsf, s1_list, None, None)
+
+
+def _zero_rows_like(fn, *shaped):
+    """`fn` on one all-zero row per argument, with the rows dropped again: the empty result with the widths / dtypes of a real one."""
+    return {k: v[:0] for k, v in fn(*[t.new_zeros((1,) + tuple(t.shape[1:])) for t in shaped]).items()}
+
+
+def _fsf_stage3(fsf, s1_list, record, replay):
     from . import voxelize as ovox
 
     cfg = fsf.cfg
-    d = dict(seg_points=s1["seg_points"], seg_logits=s1["seg_logits"], seg_vote_preds=s1["seg_vote_preds"],
-             seg_feats=s1["seg_feats"], batch_idx=s1["batch_idx"], vote_offsets=s1["offsets"])
     rng = fsf.cluster_assigner.point_cloud_range
-    if replay is not None:
-        new_coors, inv = replay["pre_new_coors"], replay["pre_inv"]
-    else:
-        coors = torch.from_numpy(ovox.divfloor_coors(d["seg_points"][:, :3].numpy(), cfg["pre_voxelization_size"], rng[:3],
-                                                     "zyx", d["batch_idx"].numpy()))
-        new_coors, inv = torch.unique(coors, return_inverse=True, dim=0)
-    if record is not None:
-        record.update(pre_new_coors=new_coors, pre_inv=inv, groups=[])
-    vox = {k: oscatter.segment_mean(v, inv, new_coors.size(0)) for k, v in d.items() if v.is_floating_point()}
-    vox["batch_idx"] = new_coors[:, 0]
-    seg_logits = vox["seg_logits"]
-    scores = seg_logits.softmax(1)
-    offset = vox["vote_offsets"].reshape(-1, fsf.num_classes + 1, 3)
+    nb = len(s1_list)
+    assert replay is None or nb == 1
     names = cfg["class_names"]
-    pts_all, feats_all, inds_all, centers_all = [], [], [], []
+    per = []
+    for s1 in s1_list:  # pre_voxelize (:585-605)
+        d = dict(seg_points=s1["seg_points"], seg_logits=s1["seg_logits"], seg_vote_preds=s1["seg_vote_preds"],
+                 seg_feats=s1["seg_feats"], batch_idx=s1["batch_idx"], vote_offsets=s1["offsets"])
+        if d["seg_points"].shape[0] == 0:
+            raise ValueError("oracle.fsf_stage3: a sample without points (the reference raises on `batch_idx.max()` of an empty tensor, "
+                             "single_stage_fsd.py:803-804)")
+        if replay is not None:
+            new_coors, inv = replay["pre_new_coors"], replay["pre_inv"]
+        else:
+            coors = torch.from_numpy(ovox.divfloor_coors(d["seg_points"][:, :3].numpy(), cfg["pre_voxelization_size"], rng[:3],
+                                                         "zyx", d["batch_idx"].numpy()))
+            new_coors, inv = torch.unique(coors, return_inverse=True, dim=0)
+        vox = {k: oscatter.segment_mean(v, inv, new_coors.size(0)) for k, v in d.items() if v.is_floating_point()}
+        vox["batch_idx"] = new_coors[:, 0]
+        per.append(dict(vox=vox, new_coors=new_coors, inv=inv, scores=vox["seg_logits"].softmax(1),
+                        offset=vox["vote_offsets"].reshape(-1, fsf.num_classes + 1, 3), pts=[], feats=[], inds=[], centers=[]))
+    if record is not None:
+        record.update(pre_new_coors=per[0]["new_coors"], pre_inv=per[0]["inv"], groups=[])
+    rules = dict(forced_first=[], inverted=[], bridged=[])
     for gi, group in enumerate(cfg["group_names"]):
         idx = [names.index(n) for n in group]
         rp = replay["groups"][gi] if replay is not None else None
-        if rp is not None:
-            fg, wgt = rp["fg"], rp["wgt"].to(seg_logits.dtype)
-        else:
-            fg = scores[:, idx].sum(1) > cfg["score_thresh"][gi]
-            if fg.sum() == 0:
-                fg[0] = True
-            lg = seg_logits[:, idx][fg]
-            wgt = ((lg - lg.max(1)[0][:, None]).abs() < 1e-6).float()
-            wgt = wgt / wgt.sum(1)[:, None]
-        centers = vox["seg_points"][fg, :3] + (offset[:, idx, :][fg] * wgt[:, :, None]).sum(1)
         vs = fsf.cluster_assigner.cluster_voxel_size[gi]
-        bidx = vox["batch_idx"][fg].int()
-        if rp is not None:
-            valid, vinv, comp = rp["valid"], rp["vinv"], rp["comp"]
-            cpts = centers[valid]
+        # group_sample (:802-865)
+        if rp is None:
+            fgs = [p["scores"][:, idx].sum(1) > cfg["score_thresh"][gi] for p in per]
+            force = any(int(fg.sum()) == 0 for fg in fgs)  # :832-834, over the batch
+            rules["forced_first"].append(force)
+            if force:
+                for fg in fgs:
+                    fg[0] = True
+        st = []
+        for b, p in enumerate(per):
+            vox = p["vox"]
+            if rp is not None:
+                fg, wgt = rp["fg"], rp["wgt"].to(vox["seg_logits"].dtype)
+            else:
+                fg = fgs[b]
+                lg = vox["seg_logits"][:, idx][fg]
+                wgt = ((lg - lg.max(1)[0][:, None]).abs() < 1e-6).float()
+                wgt = wgt / wgt.sum(1)[:, None]
+            centers = vox["seg_points"][fg, :3] + (p["offset"][:, idx, :][fg] * wgt[:, :, None]).sum(1)
+            bidx = vox["batch_idx"][fg].int()
+            e = dict(fg=fg, wgt=wgt, centers=centers, bidx=bidx)
+            if rp is None:  # ClusterAssigner.forward_single_class (:936-959)
+                e["cc"] = torch.from_numpy(ovox.divfloor_coors(centers.numpy(), vs, rng[:3], "xyz", bidx.numpy())).int()
+                _, cinv, ccnt = torch.unique(e["cc"], return_inverse=True, return_counts=True, dim=0)
+                e["valid"] = ccnt[cinv] >= fsf.cluster_assigner.min_points
+            st.append(e)
+        if rp is None:
+            invert = not any(bool(e["valid"].any()) for e in st)  # :953-954, over the batch
+            rules["inverted"].append(invert)
+            for e in st:
+                if invert:
+                    e["valid"] = ~e["valid"]
+                e["cpts"] = e["centers"][e["valid"]]
+                if e["cpts"].shape[0]:
+                    e["vc"], _, e["vinv"] = oscatter.scatter_v2(e["cpts"], e["cc"][e["valid"]], "avg")  # :962
+                else:
+                    e["vc"], e["vinv"] = e["cpts"].new_zeros((0, 3)), torch.zeros(0, dtype=torch.int64)
+            # find_connected_componets_single_batch (:69-82) over every sample's centroids, sample-major as the unique of :962 leaves them
+            vc_all = torch.cat([e["vc"] for e in st])
+            comp_all = connected_components_xy(vc_all, fsf.cluster_assigner.connected_dist[gi]) if vc_all.shape[0] else torch.zeros(0).int()
+            at = 0
+            for e in st:
+                e["comp"] = comp_all[at:at + e["vc"].shape[0]]
+                at += e["vc"].shape[0]
+            if nb > 1:  # a component that holds centroids of more than one sample
+                owner = torch.cat([torch.full((e["vc"].shape[0],), b) for b, e in enumerate(st)])
+                n_comp = int(comp_all.max()) + 1 if comp_all.numel() else 0
+                lo = torch.full((n_comp,), nb).scatter_reduce(0, comp_all.long(), owner, "amin")
+                hi = torch.full((n_comp,), -1).scatter_reduce(0, comp_all.long(), owner, "amax")
+                rules["bridged"].append(int((lo != hi).sum()))
         else:
-            cc = torch.from_numpy(ovox.divfloor_coors(centers.numpy(), vs, rng[:3], "xyz", bidx.numpy())).int()
-            _, cinv, ccnt = torch.unique(cc, return_inverse=True, return_counts=True, dim=0)
-            valid = ccnt[cinv] >= fsf.cluster_assigner.min_points
-            if not valid.any():
-                valid = ~valid
-            cpts, cco = centers[valid], cc[valid]
-            vc, vcoors, vinv = oscatter.scatter_v2(cpts, cco, "avg")
-            comp = connected_components_xy(vc, fsf.cluster_assigner.connected_dist[gi])
+            for e in st:
+                e["valid"], e["vinv"], e["comp"] = rp["valid"], rp["vinv"], rp["comp"]
+                e["cpts"] = e["centers"][e["valid"]]
         if record is not None:
-            record["groups"].append(dict(fg=fg, wgt=wgt, valid=valid, vinv=vinv, comp=comp))
-        per_pt = comp[vinv]
-        inds_all.append(torch.stack([torch.full_like(per_pt, gi), bidx[valid], per_pt], 1))
-        pts_all.append(vox["seg_points"][fg][valid])
-        feats_all.append(torch.cat([vox["seg_logits"][fg][valid], vox["seg_vote_preds"][fg][valid], vox["seg_feats"][fg][valid]], 1))
-        centers_all.append(cpts)
-    points, feats = torch.cat(pts_all), torch.cat(feats_all)
-    cluster_inds, center_preds = torch.cat(inds_all), torch.cat(centers_all)
-    cxyz, _, cinv2 = oscatter.scatter_v2(center_preds, cluster_inds, "avg")
-    f_cluster = points[:, :3] - cxyz[cinv2]
-    _, cluster_feats, out_coors = sir_forward(fsf.backbone, points, feats, cluster_inds, f_cluster)
-    return dict(cluster_feats=cluster_feats, cluster_xyz=cxyz, cluster_inds=out_coors, pts_cluster_inds=cluster_inds,
-                points=points, pre_voxel_coors=new_coors)
+            e = st[0]
+            record["groups"].append(dict(fg=e["fg"], wgt=e["wgt"], valid=e["valid"], vinv=e["vinv"], comp=e["comp"]))
+        for p, e in zip(per, st):
+            vox, fg, valid = p["vox"], e["fg"], e["valid"]
+            per_pt = e["comp"][e["vinv"]]
+            p["inds"].append(torch.stack([torch.full_like(per_pt, gi), e["bidx"][valid], per_pt], 1))
+            p["pts"].append(vox["seg_points"][fg][valid])
+            p["feats"].append(torch.cat([vox["seg_logits"][fg][valid], vox["seg_vote_preds"][fg][valid], vox["seg_feats"][fg][valid]], 1))
+            p["centers"].append(e["cpts"])
+
+    def finish(points, feats, cluster_inds, center_preds):  # extract_feat (:458-474)
+        cxyz, _, cinv2 = oscatter.scatter_v2(center_preds, cluster_inds, "avg")
+        f_cluster = points[:, :3] - cxyz[cinv2]
+        _, cluster_feats, out_coors = sir_forward(fsf.backbone, points, feats, cluster_inds, f_cluster)
+        return dict(cluster_feats=cluster_feats, cluster_xyz=cxyz, cluster_inds=out_coors, pts_cluster_inds=cluster_inds, points=points)
+
+    outs = []
+    for p in per:
+        a = (torch.cat(p["pts"]), torch.cat(p["feats"]), torch.cat(p["inds"]), torch.cat(p["centers"]))
+        out = finish(*a) if a[0].shape[0] else _zero_rows_like(finish, *a)  # (no LiDAR query: only inside a batch, see fsf_stage3_batch)
+        out.update(pre_voxel_coors=p["new_coors"], rules=rules)
+        outs.append(out)
+    return outs
 
 
 # --------------------------------------------------------------------------------------- query refinement
@@ -566,35 +666,142 @@ def get_bboxes_single(cfg, cls_logits, reg_preds, cluster_xyz, delta=1e-4, near_
 
 
 # ------------------------------------------------------------------------------ the whole frame, un-restarted
+def _check_sample(points8):
+    if points8.shape[0] == 0:
+        raise ValueError("oracle.simple_test: a sample without points.  The reference raises on it as well: `batch_idx.max()` of an "
+                         "empty tensor in group_sample (single_stage_fsd.py:803-804) — a loader's range filter that leaves nothing "
+                         "has to drop the frame")
+
+
+def _refine_and_boxes(fsf, i_stage, s1, mask_anno, img_hw, s2, s3):
+    """FSF.simple_test steps 2-4 behind the query features (FSF.py:1132-1178), one sample's queries against that sample's points."""
+    from . import refine as orefine
+
+    f_res = cluster_head_forward(fsf.frustum_obj_head, s2["obj_feat"])
+    l_res = cluster_head_forward(fsf.bbox_head, s3["cluster_feats"])
+    centers, coors, result, feats, p2d = combine_frustum_and_fsd(
+        fsf, s2["obj_centers"], s2["obj_coors"], f_res, s2["obj_feat"], s2["preds_2d"],
+        s3["cluster_xyz"], s3["cluster_inds"], l_res, s3["cluster_feats"])
+    pooled = 0
+    if centers.shape[0] == 0:  # each_stage_refine, FSF.py:1060-1062: no query -> no RoI, an empty [0, lidar_input_dim] feature
+        code = result["reg_preds"][0].shape[1]
+        rois = centers.new_zeros((0, code))  # (batch column + the decoded box: code_size - 1 + 1 columns, :1085-1094)
+        lidar_img = centers.new_zeros((0, fsf.lidar_input_dim))
+        obj_centers = centers.clone()
+    else:
+        rois = decode_stage_bboxes(centers, coors[:, 0], result["reg_preds"])
+        ext = fsf.roi_extractor
+        wp, wr, wf = orefine.dynamic_point_pool(rois[:, 1:8].numpy(), s1["seg_points"][:, :3].numpy(), ext.extra_wlh,
+                                                ext.max_inbox_point, ext.max_all_pts, stop_at_cap=True)
+        pooled = int(wp.shape[0])
+        if pooled == 0:
+            # no point inside any enlarged RoI: the pooling op fakes ONE row (point -1, RoI -1, zero features:
+            # ops/dynamic_point_pool_op.py:36-40; kept as it is by dynamic_point_roi_extractor.py:61-65).  Index -1 reads the last
+            # point / the last RoI, the refine head groups the row under RoI -1 and drops that group (fsd_bbox_head.py:148-149):
+            # every RoI gets the all-zero feature row
+            wp, wr, wf = np.full(1, -1, np.int64), np.full(1, -1, np.int64), np.zeros((1, 13), np.float32)
+        pool = (torch.from_numpy(wp), torch.from_numpy(wr), torch.from_numpy(wf))
+        lidar_img = query_feat_refine(fsf, i_stage, s1["seg_points"], s1["seg_feats"], s1["obj_id"], mask_anno, rois, pool, img_hw)
+        obj_centers = rois[:, 1:4]
+    res, query = refined_query(fsf, i_stage, lidar_img, feats, obj_centers)
+    cfg = fsf.frustum_refined_head[i_stage].test_cfg
+    rows, scs, labs, boxes, margin = get_bboxes_single(cfg, res["cls_logits"][0], res["reg_preds"][0], obj_centers)
+    return dict(boxes=boxes[rows], scores=scs, labels=labs, rows=rows, margin=margin, s1=s1, s2=s2, s3=s3,
+                query_coors=coors, query_feats=feats, rois=rois, refined_query=query, cls_logits=res["cls_logits"][0],
+                reg_preds=res["reg_preds"][0], all_boxes=boxes, pooled_points=pooled)
+
+
 def simple_test(fsf, points8, mask_data, mask_anno, lidar2img, i_stage=0):
     """FSF.simple_test (FSF.py:1114-1178) for one sample, every stage fed by the ORACLE's own previous stage (no restart
     from device intermediates): segmentor + image fusion + segmentation head (:1123-1130), camera queries (:607-650) and
     LiDAR queries (:569-600) with their heads, combine_frustum_and_fsd (:657-692), one refinement stage (:1046-1083:
     decode_stage_bboxes, RoI point pooling, refine SIR, query update, refined head) and get_bboxes
     (frustum_cluster_head.py:587-698).  Returns the final (boxes, scores, labels) and the intermediates an end-to-end
-    agreement test reports on (tests/test_e2e_agreement_gpu.py)."""
-    from . import refine as orefine
+    agreement test reports on (tests/test_e2e_agreement_gpu.py).
 
+    Degenerate frames follow the reference's own branches:
+      * no point inside any mask -> the fake camera query (FSF.py:407-414, `fsf_stage2`);
+      * no foreground pre-voxel / no dense cluster cell -> the first pre-voxel, the inverted density mask
+        (single_stage_fsd.py:832-834, :952-954, `fsf_stage3`): one sample always has >= 1 LiDAR query per class group;
+      * no query at all -> FSF.py:1060-1062 (cannot happen for one sample, see above; a sample inside a batch can get there);
+      * no point pooled into any RoI -> the pooling op's fake row, zero features for every RoI (ops/dynamic_point_pool_op.py:36-40);
+      * no box above `score_thr` -> empty boxes / scores / labels (`margin` = inf: no NMS decision was taken).
+    A sample with NO POINTS raises ValueError: the reference raises too (`batch_idx.max()` of an empty tensor,
+    single_stage_fsd.py:803-804)."""
+    _check_sample(points8)
     img_hw = tuple(mask_data.shape[-2:])
     s1 = fsf_stage1(fsf, points8, mask_data, mask_anno, lidar2img)
     s2 = fsf_stage2(fsf, s1, mask_anno, img_hw)
     s3_record = {}
     s3 = fsf_stage3(fsf, s1, record=s3_record)
-    f_res = cluster_head_forward(fsf.frustum_obj_head, s2["obj_feat"])
-    l_res = cluster_head_forward(fsf.bbox_head, s3["cluster_feats"])
-    centers, coors, result, feats, p2d = combine_frustum_and_fsd(
-        fsf, s2["obj_centers"], s2["obj_coors"], f_res, s2["obj_feat"], s2["preds_2d"],
-        s3["cluster_xyz"], s3["cluster_inds"], l_res, s3["cluster_feats"])
-    rois = decode_stage_bboxes(centers, coors[:, 0], result["reg_preds"])
-    ext = fsf.roi_extractor
-    wp, wr, wf = orefine.dynamic_point_pool(rois[:, 1:8].numpy(), s1["seg_points"][:, :3].numpy(), ext.extra_wlh,
-                                            ext.max_inbox_point, ext.max_all_pts, stop_at_cap=True)
-    pool = (torch.from_numpy(wp), torch.from_numpy(wr), torch.from_numpy(wf))
-    lidar_img = query_feat_refine(fsf, i_stage, s1["seg_points"], s1["seg_feats"], s1["obj_id"], mask_anno, rois, pool,
-                                  img_hw)
-    res, query = refined_query(fsf, i_stage, lidar_img, feats, rois[:, 1:4])
-    cfg = fsf.frustum_refined_head[i_stage].test_cfg
-    rows, scs, labs, boxes, margin = get_bboxes_single(cfg, res["cls_logits"][0], res["reg_preds"][0], rois[:, 1:4])
-    return dict(boxes=boxes[rows], scores=scs, labels=labs, rows=rows, margin=margin, s1=s1, s2=s2, s3=s3, s3_decisions=s3_record,
-                query_coors=coors, query_feats=feats, rois=rois, refined_query=query, cls_logits=res["cls_logits"][0],
-                reg_preds=res["reg_preds"][0], all_boxes=boxes)
+    out = _refine_and_boxes(fsf, i_stage, s1, mask_anno, img_hw, s2, s3)
+    out["s3_decisions"] = s3_record
+    return out
+
+
+def simple_test_batch(fsf, samples, i_stage=0, only=None):
+    """FSF.simple_test for a batch: `samples` = [(points8, mask_data, mask_anno, lidar2img)], returns one `simple_test` dict per sample
+    (keys carry the sample index in their batch column).
+
+    At inference every layer is row-wise or grouped by a key that holds the sample index (eval-mode norms, sparse convolutions per
+    batch index, scatter / unique keys with a batch column, RoI pooling and NMS per sample: dynamic_point_roi_extractor.py:45-59,
+    frustum_cluster_head.py get_bboxes_single_task), so a sample's expected result is its own single-sample result — evaluated
+    here per sample, which makes it bit-identical to `simple_test` — EXCEPT for the rules the reference states over the batch:
+
+      1. the fake camera query exists only when the WHOLE batch has no point inside a mask (`obj_id_tensor.sum() == 0` on the
+         batch's tensor, FSF.py:400-414), and then once, with key (0, 0, 0): it belongs to sample 0.  A sample without camera
+         points next to one that has some gets NO camera query;
+      2. "at least one foreground point per sample" fires for every sample when it fires for one (single_stage_fsd.py:832-834);
+      3. the density mask's inversion is decided over the batch (:952-954);
+      4. test-time connected components ignore the sample index (:69-82, :977) — rules 2-4: `fsf_stage3_batch`.
+    LiDAR cluster ids are batch-wide component labels and `combine_frustum_and_fsd` adds `fsd_begin_idx` to them (FSF.py:673):
+    ids are keys, defined up to renumbering — compare per sample as partitions (`query_partition`).
+
+    Beyond the reference: its `decode_stage_bboxes` (FSF.py:1085-1094) walks the per-TASK list `reg_preds` with the SAMPLE index and
+    so raises on any batch > 1 with the single-task heads of the configs (shape mismatch at :1091-1092); its RoI extractor adds
+    a per-sample RoI base that assumes RoIs sorted by sample (dynamic_point_roi_extractor.py:67-72), which the (camera, LiDAR) query
+    order is not.  The product decodes every query with its own centre and pools per sample by the batch column; that reading —
+    each sample's queries refined against that sample's points — is the one evaluated here.  A sample that ends with no query
+    returns no box (the reference's extractor would assert, :51).
+
+    `only`: the sample indices whose refinement and boxes are wanted (stages 1-3 always run for the whole batch — the batch rules
+    need every sample); the other entries of the result are None."""
+    img = [tuple(m.shape[-2:]) for _, m, _, _ in samples]
+    s1s = []
+    for b, (points8, mask_data, mask_anno, lidar2img) in enumerate(samples):
+        _check_sample(points8)
+        s1 = fsf_stage1(fsf, points8, mask_data, mask_anno, lidar2img)
+        s1["batch_idx"] = torch.full_like(s1["batch_idx"], b)
+        s1s.append(s1)
+    any_camera_point = any(bool((s1["obj_id"].sum((-2, -1)) > 0).any()) for s1 in s1s)
+    s2s = []
+    for b, s1 in enumerate(s1s):
+        s2 = fsf_stage2(fsf, s1, samples[b][2], img[b], fake_if_empty=(not any_camera_point and b == 0))
+        if s2["fake"]:
+            assert b == 0 and int(s2["obj_coors"][0, 0]) == 0
+        s2s.append(s2)
+    s3s = fsf_stage3_batch(fsf, s1s)
+    return [_refine_and_boxes(fsf, i_stage, s1s[b], samples[b][2], img[b], s2s[b], s3s[b]) if only is None or b in only else None
+            for b in range(len(samples))]
+
+
+def query_partition(pts_keys, pts_xyz):
+    """A query structure up to the renumbering of its ids: the set of groups of `pts_keys` [n, k] rows (camera: `s2["sir_coors"]`,
+    LiDAR: `s3["pts_cluster_inds"]`), each group as (its leading key columns but the id, the sorted tuple of its points' xyz bytes)."""
+    keys = np.asarray(pts_keys)
+    xyz = np.ascontiguousarray(np.asarray(pts_xyz, dtype=np.float32)[:, :3])
+    groups = {}
+    for i in range(keys.shape[0]):
+        groups.setdefault(tuple(keys[i].tolist()), []).append(xyz[i].tobytes())
+    return {(k[:-1], tuple(sorted(v))) for k, v in groups.items()}
+
+
+def batch_query_keys(results):
+    """The (camera, LiDAR) query key tables of a batch as `combine_frustum_and_fsd` receives them: camera keys sample-major (the
+    unique of (sample, 0, id)), LiDAR keys in the order of the unique of (group, sample, id)."""
+    cam = torch.cat([r["s2"]["obj_coors"] for r in results])
+    lid = torch.cat([r["s3"]["cluster_inds"] for r in results])
+    if lid.shape[0]:
+        order = np.lexsort((lid[:, 2].numpy(), lid[:, 1].numpy(), lid[:, 0].numpy()))
+        lid = lid[torch.from_numpy(order)]
+    return cam, lid
