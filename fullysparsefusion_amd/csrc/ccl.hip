@@ -275,7 +275,7 @@ extern "C" int fsf_connected_components_grouped(const float* points, int64_t n, 
                                                 const float* dist_table, int32_t num_groups, int32_t* labels,
                                                 int64_t* num_components_dev, void* workspace, int64_t workspace_bytes,
                                                 void* stream_) {
-  if (!group_idx || !dist_table || num_groups < 1) return FSF_ERR_INVALID_ARG;
+  if ((n > 0 && !group_idx) || !dist_table || num_groups < 1) return FSF_ERR_INVALID_ARG;  // (no points: the index of no points may be NULL)
   return ccl_run(points, n, point_stride, group_idx, 0.0f, dist_table, labels, num_components_dev, workspace, workspace_bytes,
                  (hipStream_t)stream_);
 }

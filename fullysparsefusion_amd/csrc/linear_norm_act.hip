@@ -1075,7 +1075,7 @@ static int lna_grouped(const float* x, int64_t n, int32_t k, int64_t x_stride, c
                        const float* row_add, const int64_t* row_add_index, int64_t row_add_stride, int32_t norm, const float* gamma,
                        const float* beta, float eps, int32_t act, float* out, int64_t out_stride, void* stream_, bool xf) {
   hipStream_t stream = (hipStream_t)stream_;
-  if ((row_add == nullptr) != (row_add_index == nullptr)) return FSF_ERR_INVALID_ARG;
+  if (n > 0 && (row_add == nullptr) != (row_add_index == nullptr)) return FSF_ERR_INVALID_ARG;  // (no rows: the index of no rows may be NULL)
   if (xf && (c <= 32 || ((uintptr_t)planes % 16) != 0)) return FSF_ERR_UNSUPPORTED;
   if (row_add && ((row_add_stride % 4) != 0 || row_add_stride < c || ((uintptr_t)row_add % 16) != 0)) return FSF_ERR_UNSUPPORTED;
   if (n < 0 || k < 1 || c < 1 || !planes || norm < 0 || norm > 2 || act < 0 || act > 2 || (norm != 0 && (!gamma || !beta)) ||
@@ -1114,7 +1114,7 @@ static int lna_segmax(const float* x, int64_t n, int32_t k, int64_t x_stride, co
                       int64_t seg_out_stride, float* out, int64_t out_stride, void* stream_, bool xf) {
   hipStream_t stream = (hipStream_t)stream_;
   if (xf && planes && ((uintptr_t)planes % 16) != 0) return FSF_ERR_UNSUPPORTED;
-  if ((row_add == nullptr) != (row_add_index == nullptr)) return FSF_ERR_INVALID_ARG;
+  if (n > 0 && (row_add == nullptr) != (row_add_index == nullptr)) return FSF_ERR_INVALID_ARG;  // (no rows: the index of no rows may be NULL)
   if (row_add && ((row_add_stride % 4) != 0 || row_add_stride < c || ((uintptr_t)row_add % 16) != 0)) return FSF_ERR_UNSUPPORTED;
   if (n < 0 || k < 1 || c < 1 || !planes || norm < 0 || norm > 2 || act < 0 || act > 2 || (norm != 0 && (!gamma || !beta)) ||
       num_segments < 0 || (n > 0 && (!x || !seg_ids || !seg_out || num_segments < 1)))

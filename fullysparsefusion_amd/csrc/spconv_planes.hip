@@ -1090,6 +1090,14 @@ extern "C" int fsf_spconv_prepare_weight_planes(const float* weight, int32_t kvo
   return FSF_OK;
 }
 
+// m_out == 0 with plane output: the planes still hold their zero row (row m_out = row 0: zeros, scale 1), which the next layer's missing
+// neighbours read
+__global__ void sp_zero_row_only_kernel(uint4* __restrict__ planes, float* __restrict__ scales, int nu4, int nchunk) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < nu4) planes[i] = make_uint4(0, 0, 0, 0);
+  if (i < nchunk) scales[i] = 1.0f;
+}
+
 extern "C" int fsf_spconv_forward_planes(const void* xa, const float* sa, int32_t ca, const void* xb, const float* sb, int32_t cb,
                                          int64_t m_in, const void* wplanes, int32_t kvol, int32_t cout, const int32_t* nbr,
                                          int64_t m_out, const float* scale, const float* shift, const float* residual, int32_t relu,
@@ -1102,7 +1110,14 @@ extern "C" int fsf_spconv_forward_planes(const void* xa, const float* sa, int32_
   if (kvol > SP_KVOL_MAX || (ca % 32) != 0 || (cb % 32) != 0 || ca > 128 || cb > 128 || (cout != 64 && (cout % 128) != 0) ||
       ((uintptr_t)out % 16) != 0 || ((uintptr_t)residual % 16) != 0)
     return FSF_ERR_UNSUPPORTED;
-  if (m_out == 0) return FSF_OK;
+  if (m_out == 0) {
+    if (out_planes) {
+      const int nu4 = cout * 4 / 16, nchunk = (cout + 127) / 128;
+      hipLaunchKernelGGL(sp_zero_row_only_kernel, dim3((nu4 + 255) / 256), dim3(256), 0, stream, (uint4*)out_planes, out_scales, nu4, nchunk);
+      FSF_LAUNCH_CHECK();
+    }
+    return FSF_OK;
+  }
   SpArgs a;
   a.x[0] = (const char*)xa; a.x[1] = (const char*)xb;
   a.sx[0] = sa; a.sx[1] = sb;

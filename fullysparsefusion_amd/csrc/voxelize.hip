@@ -236,8 +236,7 @@ extern "C" int fsf_voxelize_dynamic(const float* points, int64_t n, int32_t poin
                                     const float voxel_size[3], const float pc_range[6], const int32_t grid[3],
                                     int32_t* coors_zyx, int64_t* coors_bzyx, void* stream_) {
   hipStream_t stream = (hipStream_t)stream_;
-  if (n < 0 || point_stride < 3 || !voxel_size || !pc_range || !grid || (!coors_zyx && !coors_bzyx) ||
-      (n > 0 && !points))
+  if (n < 0 || point_stride < 3 || !voxel_size || !pc_range || !grid || (n > 0 && ((!coors_zyx && !coors_bzyx) || !points)))  // (no rows: NULL outputs)
     return FSF_ERR_INVALID_ARG;
   if (n == 0) return FSF_OK;
   VoxParams p{voxel_size[0], voxel_size[1], voxel_size[2], pc_range[0], pc_range[1], pc_range[2],
@@ -295,8 +294,8 @@ extern "C" int fsf_vfe_decorate(const float* features, int64_t n, int32_t feat_s
                                 int32_t out_stride, void* stream_) {
   hipStream_t stream = (hipStream_t)stream_;
   const int width = p + (with_cluster_center ? 3 : 0) + (with_voxel_center ? 3 : 0);
-  if (n < 0 || p < 3 || feat_stride < p || out_stride < width || (with_cluster_center && (!voxel_mean || !inv || vmean_stride < 3)) ||
-      (with_voxel_center && (!coors_bzyx || !voxel_size || !offset)) || (n > 0 && (!features || !out)))
+  if (n < 0 || p < 3 || feat_stride < p || out_stride < width || (with_cluster_center && (vmean_stride < 3 || (n > 0 && (!voxel_mean || !inv)))) ||
+      (with_voxel_center && (!voxel_size || !offset || (n > 0 && !coors_bzyx))) || (n > 0 && (!features || !out)))  // (no rows: NULL row tensors)
     return FSF_ERR_INVALID_ARG;
   if (n == 0) return FSF_OK;
   VfeDecoArgs a{features, (int)feat_stride, (int)p, voxel_mean, (int)vmean_stride, inv, coors_bzyx,

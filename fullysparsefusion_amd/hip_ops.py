@@ -385,7 +385,8 @@ def vfe_decorate(features, voxel_mean, inv, coors_bzyx, voxel_size, offset, with
     vm, vstride = _rows_view(voxel_mean) if with_cluster_center else (None, 3)
     inv = inv.to(torch.int64).contiguous() if with_cluster_center else None
     coors = coors_bzyx.to(torch.int64).contiguous() if with_voxel_center else None
-    check(_L().fsf_vfe_decorate(c_p(f.data_ptr()) if n else c_p(None), n, int(fstride), p, ptr(vm), int(vstride), ptr(inv), ptr(coors),
+    vmp = c_p(vm.data_ptr()) if vm is not None and vm.numel() else c_p(None)  # (a row-strided view passes as it is, like `features`)
+    check(_L().fsf_vfe_decorate(c_p(f.data_ptr()) if n else c_p(None), n, int(fstride), p, vmp, int(vstride), ptr(inv), ptr(coors),
                                 f32_array(voxel_size), f32_array(offset), int(bool(with_cluster_center)), int(bool(with_voxel_center)),
                                 ptr(buf), stride, stream_ptr()), "fsf_vfe_decorate")
     return buf[:, :width]
@@ -881,7 +882,7 @@ def remap_indices(table: torch.Tensor, index_map: torch.Tensor):
     """fsf_remap_indices: out = table >= 0 ? index_map[table] : -1 (i32, any shape)."""
     require_cuda(table, index_map)
     assert table.dtype == torch.int32 and index_map.dtype == torch.int32 and table.is_contiguous() and index_map.is_contiguous()
-    out = torch.empty_like(table)
+    out = torch.empty(table.shape, dtype=torch.int32, device=table.device)
     check(_L().fsf_remap_indices(ptr(table), table.numel(), ptr(index_map), ptr(out), stream_ptr()), "fsf_remap_indices")
     return out
 
@@ -1641,7 +1642,7 @@ def norm_act(x: torch.Tensor, gamma, beta, eps: float, norm: str, act, inplace=T
     assert x.dtype == torch.float32 and x.dim() == 2 and x.is_contiguous()
     n, c = x.shape
     if out is None:
-        out = x if inplace else torch.empty_like(x)
+        out = x if inplace else torch.empty((n, c), dtype=torch.float32, device=x.device)
     assert out.shape == (n, c) and out.dtype == torch.float32 and out.stride(1) == 1 and out.stride(0) >= c
     check(_L().fsf_norm_act(ptr(x), n, c, ptr(gamma), ptr(beta), float(eps), {"ln": 0, "affine": 1}[norm], _ACTS[act],
                             c_p(out.data_ptr()), out.stride(0), stream_ptr()), "fsf_norm_act")
@@ -1697,7 +1698,7 @@ def batch_norm_act_forward(x: torch.Tensor, scale: torch.Tensor, shift: torch.Te
     require_cuda(x, scale, shift)
     x = x.contiguous()
     n, c = x.shape
-    out = torch.empty_like(x)
+    out = torch.empty((n, c), dtype=torch.float32, device=x.device)
     check(_L().fsf_batch_norm_act_forward(ptr(x), n, c, ptr(scale.contiguous()), ptr(shift.contiguous()), int(bool(relu)),
                                           ptr(out), stream_ptr()), "fsf_batch_norm_act_forward")
     return out
@@ -1708,7 +1709,7 @@ def batch_norm_act_backward(x, grad_out, mean, invstd, scale, shift, relu: bool)
     require_cuda(x, grad_out, mean, invstd)
     x, grad_out = x.contiguous(), grad_out.contiguous()
     n, c = x.shape
-    gx = torch.empty_like(x)
+    gx = torch.empty((n, c), dtype=torch.float32, device=x.device)
     dg = torch.empty(c, dtype=torch.float32, device=x.device)
     db = torch.empty(c, dtype=torch.float32, device=x.device)
     h = _L()
@@ -1725,7 +1726,7 @@ def norm_act_backward(x: torch.Tensor, grad_out: torch.Tensor, gamma, beta, eps:
     require_cuda(x, grad_out)
     x, grad_out = x.contiguous(), grad_out.contiguous()
     n, c = x.shape
-    gx = torch.empty_like(x)
+    gx = torch.empty((n, c), dtype=torch.float32, device=x.device)
     dg = torch.empty((c,), dtype=torch.float32, device=x.device) if gamma is not None else None
     db = torch.empty((c,), dtype=torch.float32, device=x.device) if beta is not None else None
     h = _L()

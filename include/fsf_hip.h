@@ -7,6 +7,13 @@
  * the caller allocates worst-case capacity, the callee writes the count to a device scalar and, when the
  * `*_host` out-pointer is non-NULL, also synchronises the stream and stores it on the host.
  *
+ * Memory contract of every entry point (tests/test_guard_bands_gpu.py holds each of them to it):
+ *   - the workspace's contents are undefined on entry: whatever part of it an entry point needs zeroed, it zeroes itself;
+ *   - exactly `*_workspace_bytes` (`*_arena_bytes`) bytes are sufficient, and a smaller workspace is refused (FSF_ERR_WORKSPACE);
+ *   - every documented element of every output is written, whatever the buffer held before, unless the entry point says otherwise
+ *     (a capacity buffer is written up to its count; an "in/out" table is stated as such);
+ *   - nothing outside the stated extents of the outputs and outside the workspace's stated size is written.
+ *
  * Each declaration cites the reference interface it replaces.  Paths are relative to the reference repo
  * (BraveGroup/FullySparseFusion); "[UNVENDORED]" marks a symbol whose native source lives in a dependency
  * that is not in the reference tree (mmdet3d fork / spconv v1 / torch_scatter 2.0.2 / TorchEx), see SURVEY.md §2.2.
