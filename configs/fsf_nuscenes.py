@@ -4,7 +4,8 @@ projects/configs/nuScenes/FSF_nuScenes_config.py:33-411 of the reference, which 
 `fullysparsefusion_amd.compat.Config` — tests/test_config_surface.py checks both files build the same model).
 
 Only the model is described here; dataset pipelines, schedules and runtime hooks belong to the training
-control plane, which is out of scope.
+control plane, which is out of scope.  Of the train-time assigners the camera-query
+head's `HybridAssigner` is described (K37); the refine heads' `FrustumAssigner` is not built and not described.
 """
 CLASSES = ["car", "truck", "trailer", "bus", "construction_vehicle", "bicycle", "motorcycle", "pedestrian",
            "traffic_cone", "barrier"]
@@ -43,6 +44,11 @@ def _cluster_head(head_type, in_channel, train_cfg=None, **extra):
     return cfg
 
 
+# the camera-query head's train-time assigner (K37): 3-D containment first, 2-D IoU on the projected GT for the rest
+_HYBRID_ASSIGNER = dict(
+    type="HybridAssigner", num_cams=6,
+    assigner_2d=dict(type="MaxIoUAssigner", pos_iou_thr=0.7, neg_iou_thr=0.3, min_pos_iou=0.3, match_low_quality=True, ignore_iof_thr=-1),
+    assigner_3d=dict(type="PointInBoxAssigner"), class_names=CLASSES, tasks=[dict(num_class=NUM_CLASSES, class_names=CLASSES)])
 _HEAD_TEST_CFG = dict(use_rotate_nms=True, nms_pre=-1, nms_thr=0.35, score_thr=0.01, min_bbox_size=0, max_num=500)
 _sample_cfg = dict(score_thresh=SCORE_THRESH, pre_voxelization_size=(0.1, 0.1, 0.1), group_sample=True, offset_weight="max",
                    group_lens=GROUP_LENS, class_names=CLASSES, group_names=GROUPS)
@@ -88,7 +94,7 @@ model = dict(
     # camera query generation
     frustum_sir=_sir(67 + 64 + 5),
     frustum_obj_head=_cluster_head("FrustumClusterHead", 128 * 3 * 2 + 128, train_cfg=dict(), test_cfg=_HEAD_TEST_CFG,
-                                   as_rpn=False),
+                                   as_rpn=False, assigner=_HYBRID_ASSIGNER),
     encode_2d_mlp_cfg=dict(in_channel=16, mlp_channel=[128, 128], norm_cfg=LN3, act="gelu"),
     segmentor_updated_mlp=dict(in_channel=10, mlp_channel=[128, 67 + 64], norm_cfg=LN3, act="gelu"),
     mlp_cfg=dict(embed_dims=1024, norm_cfg=LN3, act="gelu", lidar_img_input_dim=128 * 3 * 2 + 128, lidar_input_dim=128 * 3 * 2),

@@ -10,12 +10,12 @@
 //   fsf_cluster_loss_backward  (K36c): dense grad_cls_logits / grad_reg_preds; the sigmoid is recomputed.  One lane per output element.
 // No float atomics and no host synchronisation: the same inputs give bit-identical outputs from run to run.
 #include "box_contain.h"
+#include "cluster_encode.h"
 #include "common.h"
 
 namespace fsf {
 
 constexpr int CL_BLOCK = 256;
-constexpr int CL_ENC_WORDS = 8;  // (log w, log l, log h, sin yaw, cos yaw, -, -, -)
 constexpr int CL_NUM_LOSSES = 5;  // cls, center, size, rot, vel
 constexpr int CL_PARTS = CL_NUM_LOSSES + 1;  // + the number of positive rows
 
@@ -25,7 +25,7 @@ struct ClusterLossWeights {
 
 // ------------------------------------------------------------------------------------------------ K36a
 // Per box: K35a's containment constants of the box enlarged by e (dims + 2e, z_bottom - e; e = 0 leaves every value as it is), the
-// coder's log(dim + 1e-6) / sin / cos (float64 functions of f32 values, rounded once), and the box's hit flag cleared.
+// coder's encoded values (cluster_encode.h), and the box's hit flag cleared.
 __global__ void __launch_bounds__(CL_BLOCK) cluster_box_prep_kernel(const float* __restrict__ boxes, int64_t num_boxes, int64_t box_stride,
                                                                     float enlarge, float* __restrict__ table, float* __restrict__ enc,
                                                                     int32_t* __restrict__ box_hit) {
@@ -35,11 +35,7 @@ __global__ void __launch_bounds__(CL_BLOCK) cluster_box_prep_kernel(const float*
   const float e2 = __fmul_rn(enlarge, 2.0f);
   box_constants(b[0], b[1], __fsub_rn(b[2], enlarge), __fadd_rn(b[3], e2), __fadd_rn(b[4], e2), __fadd_rn(b[5], e2), b[6],
                 table + k * BOX_WORDS);
-  float* t = enc + k * CL_ENC_WORDS;
-#pragma unroll
-  for (int c = 0; c < 3; ++c) t[c] = (float)log((double)__fadd_rn(b[3 + c], 1e-6f));
-  t[3] = (float)sin((double)b[6]);
-  t[4] = (float)cos((double)b[6]);
+  cluster_encode_box(b, enc + k * CL_ENC_WORDS);
   box_hit[k] = 0;
 }
 
@@ -54,7 +50,6 @@ __global__ void __launch_bounds__(CL_BLOCK) cluster_targets_kernel(const float* 
                                                                    float* __restrict__ bbox_targets, float* __restrict__ bbox_weights,
                                                                    int32_t* __restrict__ assigned, int32_t* __restrict__ box_hit,
                                                                    int32_t* __restrict__ partial_count) {
-  __shared__ int32_t wave_count[CL_BLOCK / FSF_WAVE];
   const int64_t i = (int64_t)blockIdx.x * CL_BLOCK + threadIdx.x;
   int hit_count = 0;
   if (i < n) {
@@ -67,88 +62,18 @@ __global__ void __launch_bounds__(CL_BLOCK) cluster_targets_kernel(const float* 
       k0 = box_ptr[b];
       hit = first_box_containing(q[0], q[1], q[2], table, box_labels, k0, box_ptr[b + 1]);
     }
-    float tgt[10], wgt[10];
-#pragma unroll
-    for (int c = 0; c < 10; ++c) tgt[c] = wgt[c] = 0.f;
-    int64_t lab = num_classes;
-    if (hit >= 0) {
-      const float* g = boxes + (int64_t)hit * box_stride;
-      const float* t = enc + (int64_t)hit * CL_ENC_WORDS;
-      lab = box_labels[hit];
-#pragma unroll
-      for (int c = 0; c < 3; ++c) tgt[c] = __fsub_rn(g[c], q[c]);  // the coder's centre delta: box columns 0..2 as stored
-#pragma unroll
-      for (int c = 0; c < 5; ++c) tgt[3 + c] = t[c];
-#pragma unroll
-      for (int c = 0; c < 10; ++c) wgt[c] = 1.f;
-      if (code_size == 10) {
-        tgt[8] = g[7];
-        tgt[9] = g[8];
-        if (box_cols == 10) wgt[8] = wgt[9] = g[9];  // the copy-paste flag switches the velocity columns off
-      }
-      box_hit[hit] = 1;  // (every writer stores the same word)
-      hit_count = 1;
-    }
-    labels[i] = lab;
+    hit_count = cluster_write_target_rows(i, q, hit, boxes, box_stride, box_cols, enc, box_labels, num_classes, code_size, labels,
+                                          bbox_targets, bbox_weights, box_hit);
     assigned[i] = hit >= 0 ? hit - k0 : -1;
-    float* to = bbox_targets + i * code_size;
-    float* wo = bbox_weights + i * code_size;
-    if (code_size == 10) {
-#pragma unroll
-      for (int c = 0; c < 10; ++c) {
-        to[c] = tgt[c];
-        wo[c] = wgt[c];
-      }
-    } else {
-#pragma unroll
-      for (int c = 0; c < 8; ++c) {
-        to[c] = tgt[c];
-        wo[c] = wgt[c];
-      }
-    }
   }
-  const int wsum = fsf_wave_sum(hit_count);
-  if (fsf_lane() == 0) wave_count[threadIdx.x / FSF_WAVE] = wsum;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    int s = 0;
-#pragma unroll
-    for (int w = 0; w < CL_BLOCK / FSF_WAVE; ++w) s += wave_count[w];
-    partial_count[blockIdx.x] = s;
-  }
+  cluster_block_count<CL_BLOCK>(hit_count, partial_count);
 }
 
-// stats = (num_preds, num_pos_preds, num_gts, assigned_gts, cls_avg_factor, reg_avg_factor), all f32 (integers below 2^24 are exact).
 __global__ void __launch_bounds__(CL_BLOCK) cluster_targets_final_kernel(const int32_t* __restrict__ partial, int64_t num_partials,
                                                                          const int32_t* __restrict__ box_labels,
                                                                          const int32_t* __restrict__ box_hit, int64_t num_boxes, int64_t n,
                                                                          bool hits_valid, float* __restrict__ stats) {
-  __shared__ int32_t wave_count[3][CL_BLOCK / FSF_WAVE];
-  int acc[3] = {0, 0, 0};
-  for (int64_t j = threadIdx.x; j < num_partials; j += CL_BLOCK) acc[0] += partial[j];
-  for (int64_t k = threadIdx.x; k < num_boxes; k += CL_BLOCK) {
-    acc[1] += box_labels[k] >= 0 ? 1 : 0;
-    acc[2] += (hits_valid && box_hit[k] != 0) ? 1 : 0;
-  }
-#pragma unroll
-  for (int q = 0; q < 3; ++q) {
-    const int s = fsf_wave_sum(acc[q]);
-    if (fsf_lane() == 0) wave_count[q][threadIdx.x / FSF_WAVE] = s;
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    int t[3] = {0, 0, 0};
-#pragma unroll
-    for (int q = 0; q < 3; ++q)
-#pragma unroll
-      for (int w = 0; w < CL_BLOCK / FSF_WAVE; ++w) t[q] += wave_count[q][w];
-    stats[0] = (float)n;
-    stats[1] = (float)t[0];
-    stats[2] = (float)t[1];
-    stats[3] = (float)t[2];
-    stats[4] = (float)n;
-    stats[5] = (float)t[0];
-  }
+  cluster_stats_final<CL_BLOCK>(partial, num_partials, box_labels, box_hit, num_boxes, n, hits_valid, stats);
 }
 
 // ------------------------------------------------------------------------------------------------ K36b / K36c shared

@@ -49,6 +49,22 @@ class BasePointBBoxCoder:
         return torch.cat(parts, dim=1)
 
 
+def box_corners_host(boxes7):
+    """f32 [M, >= 7] rows (x, y, z_bottom, w, l, h, yaw) -> f32 [M, 8, 3]: the vertices of the solid the containment test
+    (`points_in_boxes_first_host`, csrc/box_contain.h) tests.  Vertex v: bit 2 -> +l/2 along (cos yaw, sin yaw), bit 1 -> +w/2 across,
+    bit 0 -> the top face."""
+    b = boxes7.float()
+    yaw = b[:, 6].detach().cpu().double()
+    c, s = torch.cos(yaw).float().to(b.device), torch.sin(yaw).float().to(b.device)
+    hw, hl, top = b[:, 3] * 0.5, b[:, 4] * 0.5, b[:, 2] + b[:, 5]
+    out = []
+    for v in range(8):
+        dx = hl if v & 4 else -hl
+        dy = hw if v & 2 else -hw
+        out.append(torch.stack([(b[:, 0] + dx * c) - dy * s, (b[:, 1] + dx * s) + dy * c, top if v & 1 else b[:, 2]], 1))
+    return torch.stack(out, 1)
+
+
 class LiDARInstance3DBoxes:
     """mmdet3d 0.x LiDAR boxes, as far as the FSF heads touch them: rows (x, y, z_bottom, w, l, h, yaw[, extras])."""
 
@@ -83,6 +99,11 @@ class LiDARInstance3DBoxes:
         c = self.tensor[:, :3].clone()
         c[:, 2] = c[:, 2] + self.tensor[:, 5] * 0.5
         return c
+
+    @property
+    def corners(self):
+        """f32 [M, 8, 3]: the vertices of the solid the containment test tests (`box_corners_host`)."""
+        return box_corners_host(self.tensor[:, :7])
 
     @property
     def dims(self):

@@ -10,8 +10,12 @@ Training side: `SparseClusterHeadV2.loss` (sparse_cluster_head_v2.py:170-439 wit
 LiDAR-query head's targets and losses, on the device through K36 (docs/kernels/K36_cluster_losses.md): `fsf_cluster_targets` assigns
 every cluster centre the first GT box of its sample that contains it (K35a's pinned containment test) and encodes the box,
 `fsf_cluster_loss_forward` / `_backward` are the sigmoid focal loss + the L1 groups.  `cluster_targets_host` and
-`loss(..., fused=False)` are the torch restatement the kernels are checked against.  `SparseClusterHead.loss` (v1) and
-`FrustumClusterHead.loss` (another signature, the frustum assigner) are not built and raise.
+`loss(..., fused=False)` are the torch restatement the kernels are checked against.  `SparseClusterHead.loss` (v1) is not built.
+
+`FrustumClusterHead.loss` (frustum_cluster_head.py:96-462) — the camera-query head's: the same losses on the targets of the hybrid
+3-D / 2-D assignment (`HybridAssigner`, core/assigners.py), on the device through K37 (docs/kernels/K37_hybrid_assign.md):
+`fsf_gt_boxes_2d` projects and clips the un-augmented GT into every camera, `fsf_hybrid_assign` assigns and encodes.
+`hybrid_targets_host` is its restatement.  A head whose assigner is not a HybridAssigner (the refine heads' FrustumAssigner) raises.
 """
 from .... import switches
 import copy
@@ -21,6 +25,7 @@ import torch
 import torch.nn as nn
 
 from .... import hip_ops
+from ...core.assigners import CANVAS, HybridAssigner
 from ...core.bbox import BasePointBBoxCoder, LiDARInstance3DBoxes, box3d_multiclass_nms, xywhr2xyxyr
 from ...ops.sst_ops import build_mlp
 from ...registry import BBOX_ASSIGNERS, BBOX_CODERS, HEADS, build_head, build_loss
@@ -78,6 +83,14 @@ def cluster_targets_host(cluster_xyz, batch_idx, gt_rows_list, gt_task_labels_li
     already in the task's order: -> (labels i64 [n], label_weights f32 [n], bbox_targets f32 [n, code], bbox_weights f32 [n, code],
     assigned i64 [n] = index of the box inside its sample's valid rows or -1, stats f32 [6] = (num_preds, num_pos_preds, num_gts,
     assigned_gts, cls_avg_factor, reg_avg_factor) as totals over the batch).  Rows with label < 0 are dropped first."""
+    return _targets_from_assignment_host(
+        cluster_xyz, batch_idx, gt_rows_list, gt_task_labels_list, num_task_classes, code_size,
+        lambda b, centres, rows: points_in_boxes_first_host(centres, enlarge_box_rows(rows[:, :7], enlarge_width)))
+
+
+def _targets_from_assignment_host(cluster_xyz, batch_idx, gt_rows_list, gt_task_labels_list, num_task_classes, code_size, assign_fn):
+    """The part of `get_targets_single` every query head shares (PseudoSampler, the coder, the copy-paste flag, the log scalars):
+    `assign_fn(b, centres f32 [m, 3], rows f32 [M, D]) -> i64 [m]` names each centre's row of sample b's valid GT, or -1."""
     xyz = cluster_xyz[:, :3].float()
     n, dev = xyz.shape[0], xyz.device
     labels = torch.full((n,), num_task_classes, dtype=torch.long, device=dev)
@@ -97,7 +110,7 @@ def cluster_targets_host(cluster_xyz, batch_idx, gt_rows_list, gt_task_labels_li
         if rows.shape[0] == 0 or mine.numel() == 0:
             continue
         centres = xyz[mine]
-        inbox = points_in_boxes_first_host(centres, enlarge_box_rows(rows[:, :7], enlarge_width))
+        inbox = assign_fn(b, centres, rows).to(dev)
         pos = inbox > -1
         pos_inds, pos_gt = mine[pos], inbox[pos]
         assigned[pos_inds] = pos_gt
@@ -115,6 +128,35 @@ def cluster_targets_host(cluster_xyz, batch_idx, gt_rows_list, gt_task_labels_li
     num_pos = int((labels < num_task_classes).sum())
     stats = torch.tensor([n, num_pos, num_gts, assigned_gts, n, num_pos], dtype=torch.float32, device=dev)
     return labels, label_weights, bbox_targets, bbox_weights, assigned, stats
+
+
+def hybrid_targets_host(assigner, cluster_xyz, batch_idx, preds_2d, no_aug_rows_list, no_aug_labels_list, gt_rows_list,
+                        gt_task_labels_list, lidar2img, num_task_classes, code_size, canvas=None, return_parts=False):
+    """`FrustumClusterHead.get_targets` / `get_targets_single` with `HybridAssigner.assign` for one task on GT that is already in the
+    task's order (both lists): the tuple of `cluster_targets_host`, from the merged 3-D / 2-D assignment on the AUGMENTED GT.
+    `lidar2img` f32 [B, ncam, 4, 4].  The restatement K37 agrees with bit for bit.  With `return_parts` also a list of the per-sample
+    dicts of `HybridAssigner.assign_rows` (2-D boxes, keep flags, the 3-D and 2-D rows)."""
+    assigner.check()
+    canvas = CANVAS if canvas is None else canvas
+    lidar2img = torch.as_tensor(lidar2img).float().cpu()
+    parts = {}
+    n_samples = len(gt_rows_list)
+    assert len(no_aug_rows_list) == len(no_aug_labels_list) == n_samples == len(gt_task_labels_list)
+    p2d = preds_2d.detach().float().cpu()
+    bidx = batch_idx.detach().cpu()
+
+    def na_valid(b):
+        rows = gt_box_rows(no_aug_rows_list[b]).float().cpu()
+        lab = torch.as_tensor(no_aug_labels_list[b]).long().reshape(-1).cpu()
+        return rows[lab >= 0]
+
+    def assign_fn(b, centres, rows):
+        mine = torch.nonzero(bidx == b, as_tuple=False).reshape(-1)
+        parts[b] = assigner.assign_rows(p2d[mine], na_valid(b), centres.cpu(), rows.cpu(), lidar2img[b], canvas)
+        return parts[b]["final"]
+
+    out = _targets_from_assignment_host(cluster_xyz, batch_idx, gt_rows_list, gt_task_labels_list, num_task_classes, code_size, assign_fn)
+    return out + ([parts.get(b) for b in range(n_samples)],) if return_parts else out
 
 
 class _ClusterLossFn(torch.autograd.Function):
@@ -502,6 +544,13 @@ class SparseClusterHeadV2(SparseClusterHead):
         """:203-312.  loss_cls = focal over all rows / n; loss_center / loss_size / loss_rot = L1 over the positive rows / num_pos;
         loss_vel (when the head has it) is called upstream without avg_factor: the plain mean over the positive rows' two columns.
         Without positives the regression losses are 0 with zero gradients."""
+        return self._loss_single_task_with(self.get_targets, task_id, cls_logits, reg_preds, cluster_xyz, cluster_inds, gt_bboxes_3d,
+                                           gt_labels_3d, fused)
+
+    def _loss_single_task_with(self, get_targets, task_id, cls_logits, reg_preds, cluster_xyz, cluster_inds, gt_bboxes_3d, gt_labels_3d,
+                               fused):
+        """The losses of one task on the targets of `get_targets(num_task_classes, cluster_xyz, batch_idx, gt boxes, gt labels,
+        reg_preds, task_id, fused=)`: this head's point-in-box assignment, or the camera-query head's hybrid one."""
         self._check_loss_cfg()
         class_names = self.tasks[task_id]["class_names"]
         num_task_classes = len(class_names)
@@ -516,7 +565,7 @@ class SparseClusterHeadV2(SparseClusterHead):
         use_kernels = fused and self._fused_loss_ok(cls_logits, reg_preds, cluster_xyz)
         if not use_kernels:
             cls_logits, reg_preds, cluster_xyz = cls_logits.float(), reg_preds.float(), cluster_xyz.float()
-        labels, label_weights, bbox_targets, bbox_weights, _ = self.get_targets(
+        labels, label_weights, bbox_targets, bbox_weights, _ = get_targets(
             num_task_classes, cluster_xyz, batch_idx, gt_bboxes_3d, gt_labels_3d, reg_preds, task_id, fused=use_kernels)
         avg_factors = self._last_assignment["avg_factors"]  # (cls, reg) = (n, num_pos) as f32 scalars where the targets live
         sync = (self.sync_cls_avg_factor, self.sync_reg_avg_factor)
@@ -710,9 +759,104 @@ class FrustumClusterHead(SparseClusterHeadV2):
         self.vis_dir = vis_dir
         self.use_one_to_one = use_one_to_one
 
-    def loss(self, *args, **kwargs):
-        raise NotImplementedError("FrustumClusterHead.loss (frustum_cluster_head.py:138-265: FrustumAssigner, 2-D IoU + 3-D) is not built; "
-                                  "only the LiDAR-query head (SparseClusterHeadV2.loss) has targets and losses")
+    # ------------------------------------------------------------------------------------------- losses (K37 + K36b / K36c)
+    def _refuse_unbuilt(self):
+        if type(self.assigner) is not HybridAssigner:
+            raise NotImplementedError(
+                "FrustumClusterHead.loss (frustum_cluster_head.py:96-462) is built for a HybridAssigner only (K37); this head has "
+                f"{'no assigner' if self.assigner is None else type(self.assigner).__name__}: the refine heads' FrustumAssigner + DistAssigner "
+                "are not built")
+
+    def _check_loss_cfg(self):
+        self._refuse_unbuilt()
+        super()._check_loss_cfg()
+        if self.use_one_to_one:
+            raise NotImplementedError("FrustumClusterHead.loss: use_one_to_one=True is not used by the FSF configs and is not built")
+        if self.enlarge_width:
+            raise NotImplementedError("FrustumClusterHead.loss: enlarge_width is not read by the camera-query head's assigners")
+        self.assigner.check("FrustumClusterHead.loss: HybridAssigner")
+
+    def _lidar2img_batch(self, img_metas, device):
+        """img_metas[b]['lidar2img'] (host lists) -> f32 [B, ncam, 4, 4]: rounded to f32 on the host, one pinned non-blocking copy."""
+        import numpy as np
+
+        mats = [meta["lidar2img"] for meta in img_metas]
+        ncam = self.assigner.num_cams
+        if all(torch.is_tensor(m) for m in mats):  # (already tensors: stacked where they are)
+            stacked = torch.stack([m[:ncam].float() for m in mats])
+            assert stacked.dim() == 4 and stacked.shape[2:] == (4, 4), f"lidar2img: {tuple(stacked.shape)}"
+            if stacked.is_cuda or torch.device(device).type != "cuda":
+                return stacked.to(device)
+            return stacked.pin_memory().to(device, non_blocking=True)
+        host = torch.from_numpy(np.stack([np.stack([np.asarray(m.cpu() if torch.is_tensor(m) else m, dtype=np.float64) for m in meta][:ncam])
+                                          for meta in mats]).astype(np.float32))
+        assert host.dim() == 4 and host.shape[2:] == (4, 4), f"lidar2img: {tuple(host.shape)}"
+        if torch.device(device).type != "cuda":
+            return host
+        return host.pin_memory().to(device, non_blocking=True)
+
+    def loss(self, cls_logits, reg_preds, cluster_xyz, cluster_inds, no_aug_gt_bboxes_3d, no_aug_gt_labels_3d, gt_bboxes_3d, gt_labels_3d,
+             preds_2d=None, img_metas=None, iou_logits=None, old_cls_logits=None, old_reg_preds=None, gt_bboxes_ignore=None, fused=True):
+        """:96-136 — every task's losses and log scalars under the hybrid assignment (a query takes the augmented GT box that contains
+        its centre, else the one whose un-augmented image projection its 2-D box overlaps: docs/kernels/K37_hybrid_assign.md), keys
+        suffixed with the task's class-name list.  CUDA fp32 inputs run K37 + K36b / K36c with no host wait; `fused=False` or CPU
+        tensors run the torch restatement.  A head without a HybridAssigner raises before it looks at its arguments."""
+        self._check_loss_cfg()  # (refuses a head without a HybridAssigner first, before any argument is looked at)
+        assert isinstance(cls_logits, list) and isinstance(reg_preds, list)
+        assert len(cls_logits) == len(reg_preds) == len(self.tasks)
+        assert preds_2d is not None and img_metas is not None, "the hybrid assignment needs preds_2d and img_metas[b]['lidar2img']"
+        assert len(img_metas) == len(gt_bboxes_3d) == len(no_aug_gt_bboxes_3d)
+        lidar2img = self._lidar2img_batch(img_metas, cluster_xyz.device if fused else "cpu")
+        all_task_losses = {}
+        self.task_info = {}
+        for i in range(len(self.tasks)):
+            all_task_losses.update(self.loss_single_task(i, cls_logits[i], reg_preds[i], cluster_xyz, cluster_inds, no_aug_gt_bboxes_3d,
+                                                         no_aug_gt_labels_3d, gt_bboxes_3d, gt_labels_3d, preds_2d, img_metas,
+                                                         fused=fused, lidar2img=lidar2img))
+        return all_task_losses
+
+    def get_targets(self, num_task_classes, no_aug_gt_bboxes_3d, no_aug_gt_labels_3d, gt_bboxes_3d, gt_labels_3d, preds_2d, cluster_xyz,
+                    cluster_inds, task_id=None, img_metas_list=None, reg_preds=None, new_cls_logits=None, old_cls_logits=None,
+                    old_reg_preds=None, fused=True, lidar2img=None):
+        """:267-462 — (labels, label_weights, bbox_targets, bbox_weights, iou_labels = None) for GT already in the task's order
+        (`modify_gt_for_single_task`, both lists), and `task_info[str(task_id)]` = the four log scalars (totals over the batch)."""
+        self._check_loss_cfg()
+        batch_idx = cluster_inds if cluster_inds.ndim == 1 else cluster_inds[:, self.BATCH_COL]
+        a = self.assigner
+        on_device = fused and cluster_xyz.is_cuda and cluster_xyz.dtype == torch.float32
+        if lidar2img is None:
+            lidar2img = self._lidar2img_batch(img_metas_list, cluster_xyz.device if on_device else "cpu")
+        if on_device:
+            from .... import hip_ops_assign
+
+            dev = cluster_xyz.device
+            ptr_2d, rows_2d, labels_2d = pack_gt_for_device(no_aug_gt_bboxes_3d, no_aug_gt_labels_3d, dev, cols=7)
+            boxes_2d, keep = hip_ops_assign.gt_boxes_2d(rows_2d, labels_2d, ptr_2d, lidar2img.to(dev))
+            box_ptr, boxes, box_labels = pack_gt_for_device(gt_bboxes_3d, gt_labels_3d, dev, cols=None)
+            labels, bbox_targets, bbox_weights, assigned, stats = hip_ops_assign.hybrid_assign(
+                cluster_xyz, batch_idx, preds_2d.float(), ptr_2d, boxes_2d, keep, box_ptr, boxes, box_labels, num_task_classes,
+                self.box_code_size, a.assigner_3d.extra_height or 0.0, a.assigner_2d.pos_iou_thr, a.assigner_2d.min_pos_iou)
+            label_weights = cluster_xyz.new_ones(cluster_xyz.size(0))
+        else:
+            labels, label_weights, bbox_targets, bbox_weights, assigned, stats = hybrid_targets_host(
+                a, cluster_xyz, batch_idx, preds_2d, no_aug_gt_bboxes_3d, no_aug_gt_labels_3d, gt_bboxes_3d, gt_labels_3d, lidar2img,
+                num_task_classes, self.box_code_size)
+        self.task_info[str(task_id)] = dict(num_preds=stats[0], num_pos_preds=stats[1], num_gts=stats[2], assigned_gts=stats[3])
+        self._last_assignment = dict(assigned=assigned, avg_factors=stats[4:6])
+        return labels, label_weights, bbox_targets, bbox_weights, None
+
+    def loss_single_task(self, task_id, cls_logits, reg_preds, cluster_xyz, cluster_inds, no_aug_gt_bboxes_3d, no_aug_gt_labels_3d,
+                         gt_bboxes_3d, gt_labels_3d, preds_2d, img_metas, iou_logits=None, old_cls_logits=None, old_reg_preds=None,
+                         fused=True, lidar2img=None):
+        """:138-265.  The LiDAR-query head's losses (`SparseClusterHeadV2.loss_single_task`) on the hybrid assignment's targets."""
+        no_aug = self.modify_gt_for_single_task(no_aug_gt_bboxes_3d, no_aug_gt_labels_3d, task_id)
+
+        def targets(num_task_classes, xyz, batch_idx, gt_b, gt_l, reg_preds=None, task_id=None, fused=True):
+            return self.get_targets(num_task_classes, no_aug[0], no_aug[1], gt_b, gt_l, preds_2d, xyz, batch_idx, task_id=task_id,
+                                    img_metas_list=img_metas, reg_preds=reg_preds, fused=fused, lidar2img=lidar2img)
+
+        return self._loss_single_task_with(targets, task_id, cls_logits, reg_preds, cluster_xyz, cluster_inds, gt_bboxes_3d, gt_labels_3d,
+                                           fused)
 
     @torch.no_grad()
     def get_bboxes(self, cls_logits, reg_preds, preds_2d, cluster_xyz, cluster_inds, input_metas, iou_logits=None,

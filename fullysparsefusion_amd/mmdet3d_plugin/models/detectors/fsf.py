@@ -1006,7 +1006,7 @@ class FSF(SingleStageFSD):
         return stages
 
     def forward_train_graph(self, points, img_metas, mask_data, mask_anno, gt_bboxes_3d=None, gt_labels_3d=None,
-                            lidar_head_losses=False):
+                            lidar_head_losses=False, camera_head_losses=False, no_aug_gt_bboxes_3d=None, no_aug_gt_labels_3d=None):
         """The differentiable graph of `forward_train` (:806-903) — segmentor + image fusion + segmentation head, camera queries
         WITH `frustum_obj_head`, LiDAR queries WITH `bbox_head`, `combine_frustum_and_fsd` (both `combine_*_mlp`), and
         `multi_stage_refine_train` (:905-959: RoI point pooling, `refine_sir_layers`, `lidar_img_mlp`, `position_encoder`,
@@ -1020,7 +1020,18 @@ class FSF(SingleStageFSD):
 
         `lidar_head_losses=True` (needs the GT) also adds the LiDAR-query head's losses and log scalars, `bbox_head.loss(...)` on
         `fsd_obj_result` / `fsd_obj_centers` / `fsd_obj_coors` (:862-868), under their upstream keys `fsd_<name><class names>`, on the
-        device with no host wait (K36).  Without the flag out["losses"] has the two segmentation keys only."""
+        device with no host wait (K36).  Without the flag out["losses"] has the two segmentation keys only.
+
+        `camera_head_losses=True` (needs the GT and the un-augmented GT `no_aug_gt_bboxes_3d` / `no_aug_gt_labels_3d`: the images are
+        never augmented, so the 2-D half of the hybrid assignment projects the un-augmented boxes) also adds the camera-query head's
+        losses and log scalars, `frustum_obj_head.loss(...)` on `frustum_obj_result` / `frustum_obj_centers` / `frustum_obj_coors` /
+        `frustum_preds_2d` (:847-860), under `frustum_<name><class names>`, on the device with no host wait (K37)."""
+        if camera_head_losses:
+            for name, value in (("gt_bboxes_3d", gt_bboxes_3d), ("gt_labels_3d", gt_labels_3d),
+                                ("no_aug_gt_bboxes_3d", no_aug_gt_bboxes_3d), ("no_aug_gt_labels_3d", no_aug_gt_labels_3d)):
+                if value is None:
+                    raise ValueError(f"forward_train_graph(camera_head_losses=True) needs {name}"
+                                     + (": the images are not augmented, the augmented boxes cannot stand in" if "no_aug" in name else ""))
         self._gather_cache = None
         self._fg_cache = None
         self._img_pre = None
@@ -1045,6 +1056,11 @@ class FSF(SingleStageFSD):
                 fsd_losses = self.bbox_head.loss(l_result["cls_logits"], l_result["reg_preds"], l_centers, l_coors, gt_bboxes_3d,
                                                  gt_labels_3d, img_metas, iou_logits=l_result.get("iou_logits", None))
                 seg_losses.update({"fsd_" + k: v for k, v in fsd_losses.items()})
+            if camera_head_losses:
+                frustum_losses = self.frustum_obj_head.loss(
+                    f_result["cls_logits"], f_result["reg_preds"], f_centers, f_coors, no_aug_gt_bboxes_3d, no_aug_gt_labels_3d,
+                    gt_bboxes_3d, gt_labels_3d, f_preds_2d, img_metas, iou_logits=f_result.get("iou_logits", None))
+                seg_losses.update({"frustum_" + k: v for k, v in frustum_losses.items()})
         elif lidar_head_losses:
             raise ValueError("forward_train_graph(lidar_head_losses=True) needs gt_bboxes_3d and gt_labels_3d")
         out = dict(seg=seg_out_dict, frustum_obj_feats=f_feats, frustum_obj_centers=f_centers, frustum_obj_coors=f_coors,
@@ -1066,12 +1082,13 @@ class FSF(SingleStageFSD):
         return out
 
     def forward_train(self, points, img_metas, *args, mask_data=None, mask_anno=None, **kwargs):
-        """`forward_train` (:806-903): the graph is `forward_train_graph`, which also closes the segmentation head (K35) and the
-        LiDAR-query head (K36) with their losses; the camera head's and the refine stages' `.loss(...)` (FrustumAssigner, distance
-        assigner) are not built, so the whole training step is not either."""
+        """`forward_train` (:806-903): the graph is `forward_train_graph`, which also closes the segmentation head (K35), the
+        LiDAR-query head (K36) and the camera-query head (K37) with their losses; the refine stages' `.loss(...)` (FrustumAssigner,
+        distance assigner) is not built, so the whole training step is not either."""
         # (ADVICE r5: this used to run the whole graph and only then raise through `head.loss`)
         raise NotImplementedError(
-            "FSF.forward_train: the camera-query head's and the refine stages' target assignment and losses (`frustum_obj_head.loss`, "
-            "`frustum_refined_head.loss`, FSF.py:806-903) are not built; `forward_train_graph(points, img_metas, mask_data, mask_anno)` "
-            "returns every tensor they would consume, with `gt_bboxes_3d=..., gt_labels_3d=...` also the segmentation head's losses and "
-            "with `lidar_head_losses=True` the LiDAR-query head's (out['losses'])")
+            "FSF.forward_train: the refine stages' target assignment and losses (`frustum_refined_head.loss`: FrustumAssigner + DistAssigner, "
+            "FSF.py:806-903) are not built; `forward_train_graph(points, img_metas, mask_data, mask_anno)` "
+            "returns every tensor they would consume, with `gt_bboxes_3d=..., gt_labels_3d=...` also the segmentation head's losses, "
+            "with `lidar_head_losses=True` the LiDAR-query head's and with `camera_head_losses=True, no_aug_gt_bboxes_3d=..., "
+            "no_aug_gt_labels_3d=...` the camera-query head's (out['losses'])")

@@ -561,6 +561,46 @@ int fsf_cluster_loss_backward(const float* cls_logits, int64_t ld_cls, const flo
                               float* grad_cls_logits, float* grad_reg_preds, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * K37  camera-query head targets: hybrid 3-D / 2-D assignment (docs/kernels/K37_hybrid_assign.md)
+ * Replaces FrustumClusterHead.get_targets / get_targets_single (projects/mmdet3d_plugin/models/dense_heads/frustum_cluster_head.py:267-462),
+ *   HybridAssigner.assign / assign_2d / get_gt_bboxes_2d / prj_lidar_bbox3d_on_img / post_process_coords (core/bbox/assigners/
+ *   hybrid_assigner.py), PointInBoxAssigner (point_assigner.py) and mmdet 2.14 MaxIoUAssigner + BboxOverlaps2D + PseudoSampler.  The
+ *   losses are K36b / K36c on these targets.  Nothing here synchronises; no float atomics; no memset.
+ * K37a fsf_gt_boxes_2d: 1 launch, one lane per (box, camera); takes no scratch.
+ *   boxes       f32 rows of box_stride (>= 7) floats: the UN-AUGMENTED GT (x, y, z_bottom, w, l, h, yaw, ...) in the task's order,
+ *               box_labels i32 [num_boxes] (rows < 0 are dropped), box_ptr i32 [num_samples + 1] device: CSR of sample b's rows
+ *   lidar2img   f32 [num_samples, ncam, 4, 4] row-major, device; ncam <= 64; canvas_w / canvas_h: the image canvas (upstream: 1600, 900)
+ *   boxes_2d    f32 [num_boxes, ncam, 4] (16-byte aligned): (x1, y1, x2, y2) = bounding box of (convex hull of the eight projected
+ *               corners, clipped to [0, canvas_w] x [0, canvas_h]), zeros when dropped.  Corners: +-l/2 along (cos yaw, sin yaw), +-w/2
+ *               across, z .. z + h (the solid of K35a's containment test), f32 with cos / sin in float64 rounded once; projection =
+ *               the fma chain of K13; depth clipped to [1e-5, 1e5] before the divide; the clip in fp64, every operation rounded
+ *               separately (Liang-Barsky on the 28 corner pairs + the canvas corners inside a triangle of the corners), rounded to f32 once
+ *   keep        i32 [num_boxes, ncam]: 1 when some corner has depth > 1e-5, the hull meets the canvas and the clipped box has a width and a height
+ * K37b fsf_hybrid_assign: 4 launches (per-box constants, one wave per (2-D box, camera), one lane per query, final counts).
+ *   cluster_xyz / batch_idx / box_ptr / boxes / box_labels / num_classes / code_size / labels / bbox_targets / bbox_weights / assigned /
+ *               stats: exactly as fsf_cluster_targets (K36a), boxes being the AUGMENTED GT in the task's order
+ *   preds_2d    f32 rows of preds_stride (>= 7) floats: (x1, y1, x2, y2, score, category, camera id, ...) of query i
+ *   box_ptr_2d  i32 [num_samples + 1], boxes_2d, keep_2d, num_boxes_2d, ncam: K37a's inputs and outputs for the un-augmented GT
+ *   A query takes the FIRST box of its sample that contains its centre (K36a's test; the box grows by extra_height in z only: h + 2e,
+ *   z - e).  Failing that, among the kept 2-D boxes of its sample and camera (IoU in f32: no +1, sides clamped at 0, union floored at
+ *   1e-6): the last box j, ascending, whose own maximum IoU over that camera's queries is >= min_pos_iou and equals the query's IoU
+ *   with it; else the first box of maximum IoU when that is >= pos_iou_thr.  Index j inside the un-augmented list of the sample names
+ *   row j of the augmented one; when that row does not exist (or has a label < 0) the query stays background.
+ *   workspace: fsf_hybrid_assign_workspace_bytes(num_boxes, num_boxes_2d, ncam, n)
+ */
+int fsf_gt_boxes_2d(const float* boxes, int64_t num_boxes, int64_t box_stride, const int32_t* box_labels, const int32_t* box_ptr,
+                    int32_t num_samples, const float* lidar2img, int32_t ncam, float canvas_w, float canvas_h, float* boxes_2d,
+                    int32_t* keep, void* stream);
+int64_t fsf_hybrid_assign_workspace_bytes(int64_t num_boxes, int64_t num_boxes_2d, int32_t ncam, int64_t n);
+int fsf_hybrid_assign(const float* cluster_xyz, int64_t n, int64_t xyz_stride, const void* batch_idx, int32_t batch_idx_bytes,
+                      int64_t batch_stride, const float* preds_2d, int64_t preds_stride, const int32_t* box_ptr_2d, const float* boxes_2d,
+                      const int32_t* keep_2d, int64_t num_boxes_2d, int32_t ncam, const int32_t* box_ptr, int32_t num_samples,
+                      const float* boxes, int64_t num_boxes, int64_t box_stride, int32_t box_cols, const int32_t* box_labels,
+                      int32_t num_classes, int32_t code_size, float extra_height, float pos_iou_thr, float min_pos_iou, void* workspace,
+                      int64_t workspace_bytes, int64_t* labels, float* bbox_targets, float* bbox_weights, int32_t* assigned, float* stats,
+                      void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * K13-K15  LiDAR -> camera projection + per-point instance-mask gather
  * Replaces: FSF.prj_points_2d (projects/mmdet3d_plugin/models/detectors/FSF.py:169-200) and
  *   FSF.points_in_mask (:202-226) for one batch sample; the caller loops samples like frustum_gather (:228-258).
