@@ -2,7 +2,8 @@
 instance-id plane per camera, 26 classes, 4-d points, boxes without velocity) in the reference's config dialect — the
 model part of projects/configs/Argoverse2/FSF_AV2_config.py:10-425 (which also loads unchanged through
 `fullysparsefusion_amd.compat.Config`; tests/test_config_surface.py checks both files build the same parameters).
-Dataset pipelines / schedules / hooks and the train-time assigners are not described here."""
+Dataset pipelines / schedules / hooks are not described here; of the train-time assigners only the refine head's `FrustumAssigner`
+(no distance step on this dataset) is."""
 CLASSES = ["Regular_vehicle", "Pedestrian", "Bicyclist", "Motorcyclist", "Wheeled_rider", "Bollard", "Construction_cone", "Sign",
            "Construction_barrel", "Stop_sign", "Mobile_pedestrian_crossing_sign", "Large_vehicle", "Bus", "Box_truck", "Truck",
            "Vehicular_trailer", "Truck_cab", "School_bus", "Articulated_bus", "Message_board_trailer", "Bicycle", "Motorcycle",
@@ -100,6 +101,11 @@ model = dict(
         rel_mlp_hidden_dims=[[16, 32]] * 3, rel_mlp_in_channels=[13] * 3, reg_mlp=[512, 512], cls_mlp=[512, 512], mode="max",
         xyz_normalizer=[20, 20, 4], cat_voxel_feats=True, pos_fusion="mul", fusion="cat", act="gelu", geo_input=True,
         use_middle_cluster_feature=True, norm_cfg=LN3, unique_once=True),
-    refined_obj_head=[_cluster_head("FrustumClusterHead", 1024, test_cfg=_HEAD_TEST_CFG, as_rpn=False)],
+    # (the refine head's train-time assigner, reference :364-381: no assigner_dist on Argoverse 2; its SmoothL1Loss is not built)
+    refined_obj_head=[_cluster_head("FrustumClusterHead", 1024, test_cfg=_HEAD_TEST_CFG, as_rpn=False, assigner=dict(
+        type="FrustumAssigner", num_cams=7,
+        assigner_2d=dict(type="MaxIoUAssigner", pos_iou_thr=0.7, neg_iou_thr=0.3, min_pos_iou=0.3, match_low_quality=True,
+                         ignore_iof_thr=-1),
+        assigner_3d=dict(type="PointInBoxAssigner", extra_height=0.0), class_names=CLASSES, tasks=TASKS))],
     refine_encode_2d_mlp_cfg=dict(in_channel=32, mlp_channel=[32, 32], norm_cfg=LN3, act="gelu"),
 )

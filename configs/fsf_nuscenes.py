@@ -4,8 +4,8 @@ projects/configs/nuScenes/FSF_nuScenes_config.py:33-411 of the reference, which 
 `fullysparsefusion_amd.compat.Config` — tests/test_config_surface.py checks both files build the same model).
 
 Only the model is described here; dataset pipelines, schedules and runtime hooks belong to the training
-control plane, which is out of scope.  Of the train-time assigners the camera-query
-head's `HybridAssigner` is described (K37); the refine heads' `FrustumAssigner` is not built and not described.
+control plane, which is out of scope.  The train-time assigners are described: the camera-query
+head's `HybridAssigner` (K37) and the refine heads' `FrustumAssigner` with its `DistAssigner` radii (K38, reference :328-363).
 """
 CLASSES = ["car", "truck", "trailer", "bus", "construction_vehicle", "bicycle", "motorcycle", "pedestrian",
            "traffic_cone", "barrier"]
@@ -49,6 +49,16 @@ _HYBRID_ASSIGNER = dict(
     type="HybridAssigner", num_cams=6,
     assigner_2d=dict(type="MaxIoUAssigner", pos_iou_thr=0.7, neg_iou_thr=0.3, min_pos_iou=0.3, match_low_quality=True, ignore_iof_thr=-1),
     assigner_3d=dict(type="PointInBoxAssigner"), class_names=CLASSES, tasks=[dict(num_class=NUM_CLASSES, class_names=CLASSES)])
+# the refine heads' (K38): the same two steps, then the nearest GT of the previously predicted class inside the class's BEV radius
+_DIST_RADII = dict(car=1.0, truck=1.0, trailer=2.0, bus=4.0, construction_vehicle=0.5, bicycle=0.5, motorcycle=0.5, pedestrian=0.5,
+                   traffic_cone=0.5, barrier=0.0)
+_FRUSTUM_ASSIGNER = dict(
+    type="FrustumAssigner", num_cams=6,
+    assigner_2d=dict(type="MaxIoUAssigner", pos_iou_thr=0.7, neg_iou_thr=0.3, min_pos_iou=0.3, match_low_quality=True, ignore_iof_thr=-1),
+    assigner_3d=dict(type="PointInBoxAssigner", extra_height=0.0),
+    assigner_dist=dict(type="DistAssigner", assign_tasks=[dict(num_class=1, class_names=[name]) for name in CLASSES],
+                       max_dist=[[_DIST_RADII[name]] for name in CLASSES], class_names=CLASSES),
+    class_names=CLASSES, tasks=[dict(num_class=NUM_CLASSES, class_names=CLASSES)])
 _HEAD_TEST_CFG = dict(use_rotate_nms=True, nms_pre=-1, nms_thr=0.35, score_thr=0.01, min_bbox_size=0, max_num=500)
 _sample_cfg = dict(score_thresh=SCORE_THRESH, pre_voxelization_size=(0.1, 0.1, 0.1), group_sample=True, offset_weight="max",
                    group_lens=GROUP_LENS, class_names=CLASSES, group_names=GROUPS)
@@ -108,7 +118,7 @@ model = dict(
         reg_mlp=[512, 512], cls_mlp=[512, 512], mode="max", xyz_normalizer=[20, 20, 4], cat_voxel_feats=True, pos_fusion="mul",
         fusion="cat", act="gelu", geo_input=True, use_middle_cluster_feature=True, norm_cfg=LN3, unique_once=True),
     refined_obj_head=[
-        _cluster_head("FrustumClusterHead", 1024, test_cfg=_HEAD_TEST_CFG, as_rpn=False,
+        _cluster_head("FrustumClusterHead", 1024, train_cfg=dict(), test_cfg=_HEAD_TEST_CFG, as_rpn=False, assigner=_FRUSTUM_ASSIGNER,
                       loss_cls=dict(type="FocalLoss", use_sigmoid=True, gamma=4.0, alpha=0.25, loss_weight=2.0)),
     ],
     refine_encode_2d_mlp_cfg=dict(in_channel=10, mlp_channel=[32, 32], norm_cfg=LN3, act="gelu"),

@@ -1,6 +1,7 @@
 // The query heads' box encoding (BasePointBBoxCoder.encode with the arithmetic pinned, docs/kernels/K36_cluster_losses.md), shared by
-// K36a (cluster_loss.hip: point-in-box assignment) and K37b (hybrid_assign.hip: 3-D / 2-D hybrid assignment): one definition of the
-// per-box encoded values and of the label / target / weight rows a query gets from the box it was assigned.
+// K36a (cluster_loss.hip: point-in-box assignment), K37b and K38 (hybrid_assign.hip: 3-D / 2-D hybrid assignment, and the refine heads'
+// with the distance step): one definition of the per-box encoded values and of the label / target / weight rows a query gets from the
+// box it was assigned.
 #pragma once
 #include "common.h"
 

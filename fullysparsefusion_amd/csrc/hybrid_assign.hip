@@ -6,6 +6,9 @@
 //                             boxes of its camera (maximum IoU >= pos_iou_thr, overridden by the low-quality pass), then K36a's label /
 //                             target / weight rows, hit flags and stats.  Four launches: per-box constants, one wave per (box, camera)
 //                             for the box's maximum IoU over its camera's queries, one lane per query, one final workgroup.
+//   fsf_frustum_assign (K38): K37b with the refine heads' third step folded into the per-query kernel (a template flag): a query that
+//                             neither step assigned takes the nearest GT, in BEV, of the class the previous stage predicted for it,
+//                             when that GT is closer than the class's radius.  Same four launches; docs/kernels/K38_frustum_assign.md.
 // No float atomics, no memset, no host synchronisation: the same inputs give bit-identical outputs from run to run.
 #include "box_contain.h"
 #include "cluster_encode.h"
@@ -205,7 +208,9 @@ __global__ void __launch_bounds__(HY_BLOCK) hybrid_gt_max_kernel(const float* __
   if (fsf_lane() == 0) gt_max[t] = best;
 }
 
-template <typename BT>
+// EXT (K38): the distance step for the queries both steps left unassigned (when class_max_dist is given) and the per-query source
+// (when `source` is given).  Without EXT the branches are compiled out: K37b's results and register / scratch figures.
+template <typename BT, bool EXT>
 __global__ void __launch_bounds__(HY_BLOCK) hybrid_assign_kernel(
     const float* __restrict__ xyz, int64_t n, int64_t xyz_stride, const BT* __restrict__ batch_idx, int64_t batch_stride,
     const float* __restrict__ preds_2d, int64_t preds_stride, const int32_t* __restrict__ box_ptr_2d, const float* __restrict__ boxes_2d,
@@ -214,7 +219,8 @@ __global__ void __launch_bounds__(HY_BLOCK) hybrid_assign_kernel(
     int32_t box_cols, const float* __restrict__ table, const float* __restrict__ enc, const int32_t* __restrict__ box_labels,
     int32_t num_classes, int32_t code_size, float pos_iou_thr, float min_pos_iou, int64_t* __restrict__ labels,
     float* __restrict__ bbox_targets, float* __restrict__ bbox_weights, int32_t* __restrict__ assigned, int32_t* __restrict__ box_hit,
-    int32_t* __restrict__ partial_count) {
+    int32_t* __restrict__ partial_count, const float* __restrict__ old_cls_logits, int64_t logits_stride,
+    const float* __restrict__ class_max_dist, int32_t* __restrict__ source) {
   const int64_t i = (int64_t)blockIdx.x * HY_BLOCK + threadIdx.x;
   int hit_count = 0;
   if (i < n) {
@@ -223,10 +229,12 @@ __global__ void __launch_bounds__(HY_BLOCK) hybrid_assign_kernel(
     const int64_t b = (int64_t)batch_idx[i * batch_stride];
     int k0 = 0;
     int hit = -1;
+    int src = 0;  // 0 none, 1 3-D, 2 2-D, 3 distance
     if (b >= 0 && b < num_samples) {
       k0 = box_ptr[b];
       const int k1 = box_ptr[b + 1] < num_boxes ? box_ptr[b + 1] : (int)num_boxes;
       if (k0 >= 0) hit = first_box_containing(q[0], q[1], q[2], table, box_labels, k0, k1);  // 3-D wins
+      if (EXT && hit >= 0) src = 1;
       const float* d = preds_2d + i * preds_stride;
       const int cam = hy_query_cam(d, ncam);
       if (hit < 0 && k0 >= 0 && cam >= 0) {
@@ -249,13 +257,49 @@ __global__ void __launch_bounds__(HY_BLOCK) hybrid_assign_kernel(
         const int j = low >= 0 ? low : ((arg >= 0 && best >= pos_iou_thr) ? arg : -1);
         if (j >= 0) {  // index k inside the un-augmented list -> row k of the augmented one, background when that row does not exist
           const int k = k0 + (j - j0);
-          if (k < k1 && box_labels[k] >= 0) hit = k;
+          if (k < k1 && box_labels[k] >= 0) {
+            hit = k;
+            if (EXT) src = 2;
+          }
+        }
+      }
+      if (EXT && class_max_dist != nullptr && hit < 0 && k0 >= 0) {
+        // the class the previous stage predicted: strict > from column 0 (the lowest index wins a tie; a row of NaN gives class 0)
+        const float* lg = old_cls_logits + i * logits_stride;
+        int c = 0;
+        float top = lg[0];
+        for (int j = 1; j < num_classes; ++j) {
+          const float v = lg[j];
+          if (v > top) {
+            top = v;
+            c = j;
+          }
+        }
+        const float radius = class_max_dist[c];
+        float near = __builtin_inff();
+        int arg = -1;
+        for (int k = k0; k < k1; ++k) {  // the first row of minimum BEV distance among the sample's rows of that class
+          if (box_labels[k] != c) continue;
+          const float* g = boxes + (int64_t)k * box_stride;
+          const float dx = __fsub_rn(q[0], g[0]), dy = __fsub_rn(q[1], g[1]);
+          // sqrtf, not __fsqrt_rn: without OCML_BASIC_ROUNDED_OPERATIONS that intrinsic is the bare 1-ulp hardware root, while
+          // sqrtf is compiled to the correctly rounded sequence (the host's root, bit for bit)
+          const float d = sqrtf(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)));
+          if (d < near) {  // (a NaN or infinite distance never wins)
+            near = d;
+            arg = k;
+          }
+        }
+        if (arg >= 0 && near < radius) {
+          hit = arg;
+          src = 3;
         }
       }
     }
     hit_count = cluster_write_target_rows(i, q, hit, boxes, box_stride, box_cols, enc, box_labels, num_classes, code_size, labels,
                                           bbox_targets, bbox_weights, box_hit);
     assigned[i] = hit >= 0 ? hit - k0 : -1;
+    if (EXT && source != nullptr) source[i] = src;
   }
   cluster_block_count<HY_BLOCK>(hit_count, partial_count);
 }
@@ -297,13 +341,15 @@ extern "C" int64_t fsf_hybrid_assign_workspace_bytes(int64_t num_boxes, int64_t 
          fsf_align_up((int64_t)sizeof(float) * pairs, 256);
 }
 
-extern "C" int fsf_hybrid_assign(const float* cluster_xyz, int64_t n, int64_t xyz_stride, const void* batch_idx, int32_t batch_idx_bytes,
-                                 int64_t batch_stride, const float* preds_2d, int64_t preds_stride, const int32_t* box_ptr_2d,
-                                 const float* boxes_2d, const int32_t* keep_2d, int64_t num_boxes_2d, int32_t ncam, const int32_t* box_ptr,
-                                 int32_t num_samples, const float* boxes, int64_t num_boxes, int64_t box_stride, int32_t box_cols,
-                                 const int32_t* box_labels, int32_t num_classes, int32_t code_size, float extra_height, float pos_iou_thr,
-                                 float min_pos_iou, void* workspace, int64_t workspace_bytes, int64_t* labels, float* bbox_targets,
-                                 float* bbox_weights, int32_t* assigned, float* stats, void* stream_) {
+// K37b and K38 share everything: `ext` selects the per-query kernel with the distance step and the source output.
+static int hybrid_assign_run(const float* cluster_xyz, int64_t n, int64_t xyz_stride, const void* batch_idx, int32_t batch_idx_bytes,
+                             int64_t batch_stride, const float* preds_2d, int64_t preds_stride, const int32_t* box_ptr_2d,
+                             const float* boxes_2d, const int32_t* keep_2d, int64_t num_boxes_2d, int32_t ncam, const int32_t* box_ptr,
+                             int32_t num_samples, const float* boxes, int64_t num_boxes, int64_t box_stride, int32_t box_cols,
+                             const int32_t* box_labels, int32_t num_classes, int32_t code_size, float extra_height, float pos_iou_thr,
+                             float min_pos_iou, bool ext, const float* old_cls_logits, int64_t logits_stride, const float* class_max_dist,
+                             void* workspace, int64_t workspace_bytes, int64_t* labels, float* bbox_targets, float* bbox_weights,
+                             int32_t* assigned, int32_t* source, float* stats, void* stream_) {
   hipStream_t stream = (hipStream_t)stream_;
   if (n < 0 || num_samples < 0 || num_boxes < 0 || num_boxes_2d < 0 || num_classes < 1 || xyz_stride < 3 || batch_stride < 1 ||
       preds_stride < 7 || ncam < 1 || ncam > HY_MAX_CAMS || (batch_idx_bytes != 4 && batch_idx_bytes != 8) ||
@@ -318,6 +364,7 @@ extern "C" int fsf_hybrid_assign(const float* cluster_xyz, int64_t n, int64_t xy
   }
   if (num_boxes_2d > 0 && (!boxes_2d || !keep_2d)) return FSF_ERR_INVALID_ARG;
   if (!(min_pos_iou > -1.f)) return FSF_ERR_INVALID_ARG;  // (-1 marks a box without a query)
+  if (class_max_dist != nullptr && (logits_stride < num_classes || (n > 0 && !old_cls_logits))) return FSF_ERR_INVALID_ARG;
   if (n >= ((int64_t)1 << 24) || num_boxes >= ((int64_t)1 << 24) || num_boxes_2d >= ((int64_t)1 << 24) ||
       ((uintptr_t)boxes_2d % 16) != 0)
     return FSF_ERR_UNSUPPORTED;
@@ -347,20 +394,52 @@ extern "C" int fsf_hybrid_assign(const float* cluster_xyz, int64_t n, int64_t xy
     FSF_LAUNCH_CHECK();
   }
   if (nblk > 0) {
-    if (wide)
-      hipLaunchKernelGGL(hybrid_assign_kernel<int64_t>, dim3((unsigned)nblk), dim3(HY_BLOCK), 0, stream, cluster_xyz, n, xyz_stride,
-                         (const int64_t*)batch_idx, batch_stride, preds_2d, preds_stride, box_ptr_2d, boxes_2d, keep_2d, gt_max,
-                         num_boxes_2d, ncam, box_ptr, num_samples, boxes, num_boxes, box_stride, box_cols, table, enc, box_labels,
-                         num_classes, code_size, pos_iou_thr, min_pos_iou, labels, bbox_targets, bbox_weights, assigned, box_hit, partial);
-    else
-      hipLaunchKernelGGL(hybrid_assign_kernel<int32_t>, dim3((unsigned)nblk), dim3(HY_BLOCK), 0, stream, cluster_xyz, n, xyz_stride,
-                         (const int32_t*)batch_idx, batch_stride, preds_2d, preds_stride, box_ptr_2d, boxes_2d, keep_2d, gt_max,
-                         num_boxes_2d, ncam, box_ptr, num_samples, boxes, num_boxes, box_stride, box_cols, table, enc, box_labels,
-                         num_classes, code_size, pos_iou_thr, min_pos_iou, labels, bbox_targets, bbox_weights, assigned, box_hit, partial);
+#define FSF_HY_LAUNCH(BT, EXT)                                                                                                          \
+  hipLaunchKernelGGL((hybrid_assign_kernel<BT, EXT>), dim3((unsigned)nblk), dim3(HY_BLOCK), 0, stream, cluster_xyz, n, xyz_stride,     \
+                     (const BT*)batch_idx, batch_stride, preds_2d, preds_stride, box_ptr_2d, boxes_2d, keep_2d, gt_max, num_boxes_2d,  \
+                     ncam, box_ptr, num_samples, boxes, num_boxes, box_stride, box_cols, table, enc, box_labels, num_classes,          \
+                     code_size, pos_iou_thr, min_pos_iou, labels, bbox_targets, bbox_weights, assigned, box_hit, partial,              \
+                     old_cls_logits, logits_stride, class_max_dist, source)
+    if (wide && ext) FSF_HY_LAUNCH(int64_t, true);
+    else if (wide) FSF_HY_LAUNCH(int64_t, false);
+    else if (ext) FSF_HY_LAUNCH(int32_t, true);
+    else FSF_HY_LAUNCH(int32_t, false);
+#undef FSF_HY_LAUNCH
     FSF_LAUNCH_CHECK();
   }
   hipLaunchKernelGGL(hybrid_assign_final_kernel, dim3(1), dim3(HY_BLOCK), 0, stream, partial, (int64_t)nblk, box_labels, box_hit, num_boxes,
                      n, nblk > 0, stats);
   FSF_LAUNCH_CHECK();
   return FSF_OK;
+}
+
+extern "C" int fsf_hybrid_assign(const float* cluster_xyz, int64_t n, int64_t xyz_stride, const void* batch_idx, int32_t batch_idx_bytes,
+                                 int64_t batch_stride, const float* preds_2d, int64_t preds_stride, const int32_t* box_ptr_2d,
+                                 const float* boxes_2d, const int32_t* keep_2d, int64_t num_boxes_2d, int32_t ncam, const int32_t* box_ptr,
+                                 int32_t num_samples, const float* boxes, int64_t num_boxes, int64_t box_stride, int32_t box_cols,
+                                 const int32_t* box_labels, int32_t num_classes, int32_t code_size, float extra_height, float pos_iou_thr,
+                                 float min_pos_iou, void* workspace, int64_t workspace_bytes, int64_t* labels, float* bbox_targets,
+                                 float* bbox_weights, int32_t* assigned, float* stats, void* stream) {
+  return hybrid_assign_run(cluster_xyz, n, xyz_stride, batch_idx, batch_idx_bytes, batch_stride, preds_2d, preds_stride, box_ptr_2d,
+                           boxes_2d, keep_2d, num_boxes_2d, ncam, box_ptr, num_samples, boxes, num_boxes, box_stride, box_cols, box_labels,
+                           num_classes, code_size, extra_height, pos_iou_thr, min_pos_iou, false, nullptr, 0, nullptr, workspace,
+                           workspace_bytes, labels, bbox_targets, bbox_weights, assigned, nullptr, stats, stream);
+}
+
+extern "C" int64_t fsf_frustum_assign_workspace_bytes(int64_t num_boxes, int64_t num_boxes_2d, int32_t ncam, int64_t n) {
+  return fsf_hybrid_assign_workspace_bytes(num_boxes, num_boxes_2d, ncam, n);  // (the distance step needs no scratch of its own)
+}
+
+extern "C" int fsf_frustum_assign(const float* cluster_xyz, int64_t n, int64_t xyz_stride, const void* batch_idx, int32_t batch_idx_bytes,
+                                  int64_t batch_stride, const float* preds_2d, int64_t preds_stride, const int32_t* box_ptr_2d,
+                                  const float* boxes_2d, const int32_t* keep_2d, int64_t num_boxes_2d, int32_t ncam, const int32_t* box_ptr,
+                                  int32_t num_samples, const float* boxes, int64_t num_boxes, int64_t box_stride, int32_t box_cols,
+                                  const int32_t* box_labels, int32_t num_classes, int32_t code_size, float extra_height, float pos_iou_thr,
+                                  float min_pos_iou, const float* old_cls_logits, int64_t logits_stride, const float* class_max_dist,
+                                  void* workspace, int64_t workspace_bytes, int64_t* labels, float* bbox_targets, float* bbox_weights,
+                                  int32_t* assigned, int32_t* source, float* stats, void* stream) {
+  return hybrid_assign_run(cluster_xyz, n, xyz_stride, batch_idx, batch_idx_bytes, batch_stride, preds_2d, preds_stride, box_ptr_2d,
+                           boxes_2d, keep_2d, num_boxes_2d, ncam, box_ptr, num_samples, boxes, num_boxes, box_stride, box_cols, box_labels,
+                           num_classes, code_size, extra_height, pos_iou_thr, min_pos_iou, true, old_cls_logits, logits_stride,
+                           class_max_dist, workspace, workspace_bytes, labels, bbox_targets, bbox_weights, assigned, source, stats, stream);
 }

@@ -1,5 +1,7 @@
 """The camera-query head's label assigners: `HybridAssigner` (projects/mmdet3d_plugin/core/bbox/assigners/hybrid_assigner.py),
-`PointInBoxAssigner` (point_assigner.py) and mmdet 2.14 `MaxIoUAssigner` with `BboxOverlaps2D`.
+`PointInBoxAssigner` (point_assigner.py) and mmdet 2.14 `MaxIoUAssigner` with `BboxOverlaps2D`; and the refine heads':
+`FrustumAssigner` (frustum_assigner.py) = `HybridAssigner` + `DistAssigner` (dist_assigner.py), on the device through K38
+(docs/kernels/K38_frustum_assign.md: `fsf_frustum_assign`, the distance step inside K37b's per-query kernel).
 
 The classes hold the configuration under the upstream constructor arguments and assign ONE sample on the host (`assign`): that is the
 unfused path and the restatement the kernels are pinned to.  The training step itself goes through K37
@@ -245,8 +247,7 @@ class HybridAssigner:
         """What no FSF config sets for the camera-query head is refused by name, not approximated."""
         if self.is_frustum:
             raise NotImplementedError(f"{who}: is_frustum=True is not used by the FSF configs and is not built")
-        if self.assigner_dist is not None:
-            raise NotImplementedError(f"{who}: assigner_dist is the refine heads' (FrustumAssigner + DistAssigner) and is not built")
+        self._check_dist(who)
         if type(self.assigner_3d) is not PointInBoxAssigner or type(self.assigner_2d) is not MaxIoUAssigner:
             raise NotImplementedError(f"{who}: assigner_3d must be a PointInBoxAssigner and assigner_2d a MaxIoUAssigner (both set)")
         a = self.assigner_2d
@@ -254,6 +255,11 @@ class HybridAssigner:
             raise NotImplementedError(f"{who}: match_low_quality=False / gt_max_assign_all=False are not used by the FSF configs and are not built")
         if a.ignore_iof_thr > 0:
             raise NotImplementedError(f"{who}: ignore_iof_thr > 0 is not used by the FSF configs and is not built")
+
+    def _check_dist(self, who):
+        if self.assigner_dist is not None:
+            raise NotImplementedError(f"{who}: assigner_dist is the refine heads' (FrustumAssigner + DistAssigner) and is not built "
+                                      "into a HybridAssigner")
 
     def assign_2d_rows(self, preds_2d, no_aug_rows, lidar2img, canvas=CANVAS):
         """`assign_2d` for one sample: -> (row of the un-augmented GT per query or -1, boxes_2d, keep)."""
@@ -292,6 +298,188 @@ class HybridAssigner:
         na_rows = getattr(no_aug_gt_bboxes_3d, "tensor", no_aug_gt_bboxes_3d)
         r = self.assign_rows(preds_2d, na_rows, cluster_xyz, gt_rows, img_metas["lidar2img"])
         labels = torch.as_tensor(gt_labels_3d).long().cpu()
+
+        def result(rows):
+            lab = torch.full_like(rows, -1)
+            lab[rows >= 0] = labels[rows[rows >= 0]]
+            return AssignResult(gt_rows.shape[0], rows + 1, None, labels=lab)
+
+        return result(r["final"]), result(r["rows_3d"]), result(r["rows_2d"])
+
+
+# ----------------------------------------------------------------------------------------------------- the refine heads' (K38)
+def bev_distance_host(query_xy, gt_xy):
+    """BEV distances f32 [n, M] with the arithmetic pinned as K38 computes it: dx = qx - gx, dy = qy - gy, fl(fl(dx dx) + fl(dy dy))
+    (no fma), a correctly rounded square root: the float64 root of an f32 value rounds to the correctly rounded f32 root, which
+    ATen's f32 sqrt need not be.  Upstream's `torch.cdist` is this up to its matmul form (docs/kernels/K38)."""
+    q, g = query_xy.float(), gt_xy.float()
+    dx, dy = q[:, None, 0] - g[None, :, 0], q[:, None, 1] - g[None, :, 1]
+    return (dx * dx + dy * dy).double().sqrt().float()
+
+
+def first_argmax_host(logits, num_classes):
+    """Arg-max of columns 0 .. num_classes - 1 by a strict `>` scan from column 0: the lowest index wins a tie, a row of NaN gives 0."""
+    logits = logits.float()
+    n = logits.shape[0]
+    arg = torch.zeros((n,), dtype=torch.long, device=logits.device)
+    if n == 0:
+        return arg
+    top = logits[:, 0].clone()
+    for j in range(1, num_classes):
+        better = logits[:, j] > top
+        top = torch.where(better, logits[:, j], top)
+        arg = torch.where(better, torch.full_like(arg, j), arg)
+    return arg
+
+
+class _ScopeFromCheck:
+    """`OUT_OF_SCOPE` for the assigners whose scope depends on their configuration (the stand-ins' is a class constant)."""
+
+    @property
+    def OUT_OF_SCOPE(self):
+        """True when this instance's configuration is one `check()` refuses."""
+        try:
+            self.check()
+        except NotImplementedError:
+            return True
+        return False
+
+
+@BBOX_ASSIGNERS.register_module()
+class DistAssigner(_ScopeFromCheck):
+    """`DistAssigner` (core/bbox/assigners/dist_assigner.py): a query takes the nearest GT, in BEV, of the class its logits predict,
+    when that GT is closer than the class's radius.  Upstream's constructor arguments; all default to None so that a config naming the
+    class alone still builds (and is refused by `check`)."""
+
+    def __init__(self, assign_tasks=None, class_names=None, max_dist=None):
+        self.tasks, self.class_names, self.max_dist = assign_tasks, class_names, max_dist
+        self.num_tasks = len(assign_tasks) if assign_tasks is not None else 0
+
+    def check(self, who="DistAssigner"):
+        """One class per assign task, every class at most once: upstream's mapping back from the per-task index to the GT list is
+        inconsistent for anything else, which is refused by name."""
+        if self.tasks is None or self.class_names is None or self.max_dist is None:
+            raise NotImplementedError(f"{who}: assign_tasks, class_names and max_dist must all be set")
+        if len(self.max_dist) != len(self.tasks):
+            raise NotImplementedError(f"{who}: max_dist needs one entry per assign_tasks entry")
+        seen = set()
+        for task, dist in zip(self.tasks, self.max_dist):
+            names = list(task["class_names"])
+            if len(names) != 1:
+                raise NotImplementedError(f"{who}: assign_tasks entries with more than one class ({names}) are not built: upstream maps "
+                                          "their per-task indices back to the GT list inconsistently")
+            if names[0] in seen:
+                raise NotImplementedError(f"{who}: class '{names[0]}' is named in two assign_tasks entries, which is not built")
+            if names[0] not in self.class_names:
+                raise NotImplementedError(f"{who}: class '{names[0]}' of assign_tasks is not in class_names")
+            if len(dist) != 1:
+                raise NotImplementedError(f"{who}: max_dist needs one radius per class of its assign_tasks entry")
+            seen.add(names[0])
+
+    def class_table(self, num_task_classes=None):
+        """f32 [C]: the radius of every class of `class_names` (the first `num_task_classes`), 0 for a class in no assign task."""
+        self.check()
+        c = len(self.class_names) if num_task_classes is None else int(num_task_classes)
+        radius = {task["class_names"][0]: float(dist[0]) for task, dist in zip(self.tasks, self.max_dist)}
+        return torch.tensor([radius.get(name, 0.0) for name in list(self.class_names)[:c]] + [0.0] * max(0, c - len(self.class_names)),
+                            dtype=torch.float32)
+
+    def assign_rows(self, cluster_xyz, cluster_logits, gt_rows, gt_labels):
+        """One sample: query centres [n, >= 2], their logits [n, >= C], GT rows [M, >= 2] with labels i64 [M] (indices into
+        `class_names`; rows < 0 are skipped) -> i64 [n]: the assigned GT row or -1."""
+        n, m = cluster_xyz.shape[0], gt_rows.shape[0]
+        out = torch.full((n,), -1, dtype=torch.long)
+        if n == 0 or m == 0:
+            return out
+        table = self.class_table()
+        c = table.numel()
+        labels = torch.as_tensor(gt_labels).long().reshape(-1).cpu()
+        pred = first_argmax_host(cluster_logits.detach().cpu()[:, :c], c)
+        d = bev_distance_host(cluster_xyz.detach().cpu()[:, :2], gt_rows.detach().cpu()[:, :2])
+        d = torch.where(torch.isfinite(d) & (labels[None, :] == pred[:, None]), d, torch.full_like(d, float("inf")))
+        near = d.min(1)[0]
+        idx = torch.arange(m)[None, :].expand(n, m)
+        arg = torch.where(d == near[:, None], idx, torch.full_like(idx, m)).min(1)[0]  # the first row of minimum distance
+        ok = near < table[pred]  # (inf, the marker of "no candidate", compares false)
+        out[ok] = arg[ok]
+        return out
+
+    def assign(self, cluster_xyz, cluster_logits, gt_bboxes_3d, gt_labels):
+        """Upstream's signature for one sample (labels are indices into `class_names`)."""
+        rows = getattr(gt_bboxes_3d, "tensor", gt_bboxes_3d)
+        labels = torch.as_tensor(gt_labels).long().reshape(-1).cpu()
+        hit = self.assign_rows(cluster_xyz, cluster_logits, rows, labels)
+        lab = torch.zeros_like(hit)  # (upstream's combine_assign_result starts from zeros)
+        lab[hit >= 0] = labels[hit[hit >= 0]]
+        return AssignResult(rows.shape[0], hit + 1, None, labels=lab)
+
+
+@BBOX_ASSIGNERS.register_module()
+class FrustumAssigner(HybridAssigner, _ScopeFromCheck):
+    """`FrustumAssigner` (core/bbox/assigners/frustum_assigner.py): `HybridAssigner`'s two steps, then `assigner_dist` for the queries
+    they left unassigned.  Without an `assigner_dist` it is the hybrid assignment."""
+
+    def __init__(self, assigner_2d=None, assigner_3d=None, assigner_dist=None, num_cams=6,
+                 class_names=["car", "truck", "construction_vehicle", "bus", "trailer", "barrier", "motorcycle", "bicycle", "pedestrian",
+                              "traffic_cone"], tasks=None, is_frustum=False, vis_dir=None, ignore_bev_dist=None):
+        super().__init__(assigner_2d, assigner_3d, assigner_dist, num_cams, class_names, tasks, is_frustum)
+        self.vis_dir, self.ignore_bev_dist = vis_dir, ignore_bev_dist
+
+    def check(self, who="FrustumAssigner", head_tasks=None, head_class_names=None):
+        """`head_tasks` / `head_class_names`: the tasks and class names of the head that owns the assigner, held to the same rule as
+        the assigner's own (`_check_labels`)."""
+        if self.vis_dir is not None:
+            raise NotImplementedError(f"{who}: vis_dir (upstream's debugging pictures) is not built")
+        if self.ignore_bev_dist is not None:
+            raise NotImplementedError(f"{who}: ignore_bev_dist is not used by the FSF configs and is not built")
+        super().check(who)
+        if head_tasks is not None or head_class_names is not None:
+            self._check_labels(who, head_tasks, head_class_names)
+
+    def _check_dist(self, who):
+        dist = self.assigner_dist
+        if dist is None:
+            return
+        if type(dist) is not DistAssigner:
+            raise NotImplementedError(f"{who}: assigner_dist must be a DistAssigner, not a {type(dist).__name__}")
+        dist.check(f"{who}: DistAssigner")
+        self._check_labels(who, self.tasks, self.class_names)
+
+    def _check_labels(self, who, tasks, class_names):
+        """DistAssigner compares task-local labels with indices into its own class_names: one task of exactly those names."""
+        dist = self.assigner_dist
+        if dist is None:
+            return
+        if tasks is None or len(tasks) != 1 or class_names is None or list(tasks[0]["class_names"]) != list(class_names) \
+                or list(dist.class_names) != list(class_names):
+            raise NotImplementedError(f"{who}: assigner_dist needs task-local labels that are the global class indices (a single task "
+                                      "whose class_names equal the head's, the assigner's and the DistAssigner's); anything else is "
+                                      "not built")
+
+    def assign_rows(self, preds_2d, no_aug_rows, cluster_xyz, gt_rows, lidar2img, canvas=CANVAS, old_cls_logits=None, gt_labels=None):
+        """`HybridAssigner.assign_rows` plus rows_dist (the distance step's row for EVERY query, -1 none) and source i64 [n]
+        (0 none, 1 3-D, 2 2-D, 3 distance); `final` takes the distance row where both other steps gave none."""
+        self.check()
+        r = HybridAssigner.assign_rows(self, preds_2d, no_aug_rows, cluster_xyz, gt_rows, lidar2img, canvas)
+        n = cluster_xyz.shape[0]
+        rows_dist = torch.full((n,), -1, dtype=torch.long)
+        if self.assigner_dist is not None:
+            if old_cls_logits is None or gt_labels is None:
+                raise ValueError("FrustumAssigner.assign_rows: the distance step needs old_cls_logits and gt_labels")
+            rows_dist = self.assigner_dist.assign_rows(cluster_xyz, old_cls_logits, gt_rows, gt_labels)
+        final = torch.where(r["final"] >= 0, r["final"], rows_dist)
+        source = torch.where(r["rows_3d"] >= 0, 1, torch.where(r["rows_2d"] >= 0, 2, torch.where(rows_dist >= 0, 3, 0)))
+        r.update(final=final, rows_dist=rows_dist, source=source.long())
+        return r
+
+    def assign(self, preds_2d, no_aug_gt_bboxes_3d, no_aug_gt_labels_3d, cluster_xyz, old_cluster_logits, old_reg_preds, gt_bboxes_3d,
+               gt_labels_3d, img_metas, task_id):
+        """Upstream's signature for one sample: -> (final, 3-D, 2-D) `AssignResult`s; labels are the augmented list's."""
+        gt_rows = getattr(gt_bboxes_3d, "tensor", gt_bboxes_3d)
+        na_rows = getattr(no_aug_gt_bboxes_3d, "tensor", no_aug_gt_bboxes_3d)
+        labels = torch.as_tensor(gt_labels_3d).long().cpu()
+        r = self.assign_rows(preds_2d, na_rows, cluster_xyz, gt_rows, img_metas["lidar2img"], old_cls_logits=old_cluster_logits,
+                             gt_labels=labels)
 
         def result(rows):
             lab = torch.full_like(rows, -1)

@@ -15,7 +15,12 @@ every cluster centre the first GT box of its sample that contains it (K35a's pin
 `FrustumClusterHead.loss` (frustum_cluster_head.py:96-462) — the camera-query head's: the same losses on the targets of the hybrid
 3-D / 2-D assignment (`HybridAssigner`, core/assigners.py), on the device through K37 (docs/kernels/K37_hybrid_assign.md):
 `fsf_gt_boxes_2d` projects and clips the un-augmented GT into every camera, `fsf_hybrid_assign` assigns and encodes.
-`hybrid_targets_host` is its restatement.  A head whose assigner is not a HybridAssigner (the refine heads' FrustumAssigner) raises.
+`hybrid_targets_host` is its restatement.
+
+The refine stages' heads are the same class with a `FrustumAssigner`: the hybrid assignment plus `DistAssigner`'s third step (a query
+both steps left unassigned takes the nearest GT, in BEV, of the class the previous stage predicted for it, inside the class's radius),
+on the device through K38 (docs/kernels/K38_frustum_assign.md: `fsf_frustum_assign`, the step folded into K37b's per-query kernel).
+`frustum_targets_host` is its restatement.  A head with neither assigner raises.
 """
 from .... import switches
 import copy
@@ -25,7 +30,7 @@ import torch
 import torch.nn as nn
 
 from .... import hip_ops
-from ...core.assigners import CANVAS, HybridAssigner
+from ...core.assigners import CANVAS, FrustumAssigner, HybridAssigner
 from ...core.bbox import BasePointBBoxCoder, LiDARInstance3DBoxes, box3d_multiclass_nms, xywhr2xyxyr
 from ...ops.sst_ops import build_mlp
 from ...registry import BBOX_ASSIGNERS, BBOX_CODERS, HEADS, build_head, build_loss
@@ -136,10 +141,31 @@ def hybrid_targets_host(assigner, cluster_xyz, batch_idx, preds_2d, no_aug_rows_
     task's order (both lists): the tuple of `cluster_targets_host`, from the merged 3-D / 2-D assignment on the AUGMENTED GT.
     `lidar2img` f32 [B, ncam, 4, 4].  The restatement K37 agrees with bit for bit.  With `return_parts` also a list of the per-sample
     dicts of `HybridAssigner.assign_rows` (2-D boxes, keep flags, the 3-D and 2-D rows)."""
+    return _hybrid_targets_host(assigner, cluster_xyz, batch_idx, preds_2d, no_aug_rows_list, no_aug_labels_list, gt_rows_list,
+                                gt_task_labels_list, lidar2img, num_task_classes, code_size, None, canvas, return_parts)
+
+
+def frustum_targets_host(assigner, cluster_xyz, batch_idx, preds_2d, no_aug_rows_list, no_aug_labels_list, gt_rows_list,
+                         gt_task_labels_list, lidar2img, num_task_classes, code_size, old_cls_logits=None, canvas=None,
+                         return_parts=False):
+    """`hybrid_targets_host` for a `FrustumAssigner`: the same tuple from the merged 3-D / 2-D / distance assignment.
+    `old_cls_logits` [n, >= num_task_classes] are the previous stage's logits of this task (needed when the assigner has an
+    `assigner_dist`; without one the result is `hybrid_targets_host`'s).  The restatement K38 agrees with bit for bit.  The per-sample
+    dicts of `return_parts` also hold `rows_dist` and `source` (0 none, 1 3-D, 2 2-D, 3 distance) for the sample's queries."""
+    if assigner.assigner_dist is not None and old_cls_logits is None:
+        raise ValueError("frustum_targets_host: an assigner with an assigner_dist needs old_cls_logits")
+    return _hybrid_targets_host(assigner, cluster_xyz, batch_idx, preds_2d, no_aug_rows_list, no_aug_labels_list, gt_rows_list,
+                                gt_task_labels_list, lidar2img, num_task_classes, code_size, old_cls_logits, canvas, return_parts)
+
+
+def _hybrid_targets_host(assigner, cluster_xyz, batch_idx, preds_2d, no_aug_rows_list, no_aug_labels_list, gt_rows_list,
+                         gt_task_labels_list, lidar2img, num_task_classes, code_size, old_cls_logits, canvas, return_parts):
     assigner.check()
     canvas = CANVAS if canvas is None else canvas
     lidar2img = torch.as_tensor(lidar2img).float().cpu()
     parts = {}
+    with_dist = getattr(assigner, "assigner_dist", None) is not None
+    old = old_cls_logits.detach().float().cpu()[:, :num_task_classes] if with_dist else None
     n_samples = len(gt_rows_list)
     assert len(no_aug_rows_list) == len(no_aug_labels_list) == n_samples == len(gt_task_labels_list)
     p2d = preds_2d.detach().float().cpu()
@@ -152,7 +178,12 @@ def hybrid_targets_host(assigner, cluster_xyz, batch_idx, preds_2d, no_aug_rows_
 
     def assign_fn(b, centres, rows):
         mine = torch.nonzero(bidx == b, as_tuple=False).reshape(-1)
-        parts[b] = assigner.assign_rows(p2d[mine], na_valid(b), centres.cpu(), rows.cpu(), lidar2img[b], canvas)
+        if isinstance(assigner, FrustumAssigner):
+            lab = torch.as_tensor(gt_task_labels_list[b]).long().reshape(-1).cpu()
+            parts[b] = assigner.assign_rows(p2d[mine], na_valid(b), centres.cpu(), rows.cpu(), lidar2img[b], canvas,
+                                            old_cls_logits=old[mine] if with_dist else None, gt_labels=lab[lab >= 0])
+        else:
+            parts[b] = assigner.assign_rows(p2d[mine], na_valid(b), centres.cpu(), rows.cpu(), lidar2img[b], canvas)
         return parts[b]["final"]
 
     out = _targets_from_assignment_host(cluster_xyz, batch_idx, gt_rows_list, gt_task_labels_list, num_task_classes, code_size, assign_fn)
@@ -761,11 +792,10 @@ class FrustumClusterHead(SparseClusterHeadV2):
 
     # ------------------------------------------------------------------------------------------- losses (K37 + K36b / K36c)
     def _refuse_unbuilt(self):
-        if type(self.assigner) is not HybridAssigner:
+        if type(self.assigner) not in (HybridAssigner, FrustumAssigner):
             raise NotImplementedError(
-                "FrustumClusterHead.loss (frustum_cluster_head.py:96-462) is built for a HybridAssigner only (K37); this head has "
-                f"{'no assigner' if self.assigner is None else type(self.assigner).__name__}: the refine heads' FrustumAssigner + DistAssigner "
-                "are not built")
+                "FrustumClusterHead.loss (frustum_cluster_head.py:96-462) is built for a HybridAssigner (K37) or a FrustumAssigner (K38); "
+                f"this head has {'no assigner' if self.assigner is None else 'a ' + type(self.assigner).__name__}")
 
     def _check_loss_cfg(self):
         self._refuse_unbuilt()
@@ -774,7 +804,40 @@ class FrustumClusterHead(SparseClusterHeadV2):
             raise NotImplementedError("FrustumClusterHead.loss: use_one_to_one=True is not used by the FSF configs and is not built")
         if self.enlarge_width:
             raise NotImplementedError("FrustumClusterHead.loss: enlarge_width is not read by the camera-query head's assigners")
-        self.assigner.check("FrustumClusterHead.loss: HybridAssigner")
+        who = f"FrustumClusterHead.loss: {type(self.assigner).__name__}"
+        if type(self.assigner) is FrustumAssigner:  # (the rule on task-local labels is the assigner's, applied to this head's tasks too)
+            self.assigner.check(who, head_tasks=self.tasks, head_class_names=self.class_names)
+        else:
+            self.assigner.check(who)
+
+    def _with_dist(self):
+        return type(self.assigner) is FrustumAssigner and self.assigner.assigner_dist is not None
+
+    def _dist_table(self, num_task_classes, device):
+        """The DistAssigner's per-class radii f32 [C], uploaded once per head and device (pinned, non-blocking)."""
+        cache = self.__dict__.setdefault("_dist_tables", {})
+        key = (int(num_task_classes), str(device))
+        if key not in cache:
+            host = self.assigner.assigner_dist.class_table(num_task_classes)
+            cache[key] = host.pin_memory().to(device, non_blocking=True) if torch.device(device).type == "cuda" else host
+        return cache[key]
+
+    def _source_ids(self, device):
+        cache = self.__dict__.setdefault("_source_id_rows", {})
+        if str(device) not in cache:
+            host = torch.arange(4, dtype=torch.int32)
+            cache[str(device)] = host.pin_memory().to(device, non_blocking=True) if torch.device(device).type == "cuda" else host
+        return cache[str(device)]
+
+    def gt_boxes_2d_pack(self, task_id, no_aug_gt_bboxes_3d, no_aug_gt_labels_3d, lidar2img, device):
+        """K37a for one task: the un-augmented GT regrouped in the task's order, projected and clipped into every camera ->
+        (ptr_2d, boxes_2d, keep), what `loss(..., boxes_2d_packs={task_id: pack})` takes instead of running K37a itself."""
+        from .... import hip_ops_assign
+
+        rows, labels = self.modify_gt_for_single_task(no_aug_gt_bboxes_3d, no_aug_gt_labels_3d, task_id)
+        ptr_2d, rows_2d, labels_2d = pack_gt_for_device(rows, labels, device, cols=7)
+        boxes_2d, keep = hip_ops_assign.gt_boxes_2d(rows_2d, labels_2d, ptr_2d, lidar2img.to(device))
+        return ptr_2d, boxes_2d, keep
 
     def _lidar2img_batch(self, img_metas, device):
         """img_metas[b]['lidar2img'] (host lists) -> f32 [B, ncam, 4, 4]: rounded to f32 on the host, one pinned non-blocking copy."""
@@ -796,12 +859,23 @@ class FrustumClusterHead(SparseClusterHeadV2):
         return host.pin_memory().to(device, non_blocking=True)
 
     def loss(self, cls_logits, reg_preds, cluster_xyz, cluster_inds, no_aug_gt_bboxes_3d, no_aug_gt_labels_3d, gt_bboxes_3d, gt_labels_3d,
-             preds_2d=None, img_metas=None, iou_logits=None, old_cls_logits=None, old_reg_preds=None, gt_bboxes_ignore=None, fused=True):
+             preds_2d=None, img_metas=None, iou_logits=None, old_cls_logits=None, old_reg_preds=None, gt_bboxes_ignore=None, fused=True,
+             boxes_2d_packs=None):
         """:96-136 — every task's losses and log scalars under the hybrid assignment (a query takes the augmented GT box that contains
         its centre, else the one whose un-augmented image projection its 2-D box overlaps: docs/kernels/K37_hybrid_assign.md), keys
         suffixed with the task's class-name list.  CUDA fp32 inputs run K37 + K36b / K36c with no host wait; `fused=False` or CPU
-        tensors run the torch restatement.  A head without a HybridAssigner raises before it looks at its arguments."""
-        self._check_loss_cfg()  # (refuses a head without a HybridAssigner first, before any argument is looked at)
+        tensors run the torch restatement.  A head without a built assigner raises before it looks at its arguments.
+
+        The refine stages' heads (a `FrustumAssigner` with an `assigner_dist`) also take `old_cls_logits`, the previous stage's
+        per-task class logits: a query both steps left unassigned takes the nearest GT of the class they predict, inside that class's
+        radius (K38).  `old_reg_preds` is accepted and unused, as upstream's PointInBoxAssigner ignores it.  `boxes_2d_packs`:
+        optionally {task id: `gt_boxes_2d_pack(...)`}, K37a's output computed by the caller (two heads sharing one projection)."""
+        self._check_loss_cfg()  # (refuses a head without a built assigner first, before any argument is looked at)
+        if self._with_dist():
+            if old_cls_logits is None:
+                raise ValueError("FrustumClusterHead.loss: a FrustumAssigner with an assigner_dist needs old_cls_logits (the previous "
+                                 "stage's class logits, one tensor per task)")
+            assert isinstance(old_cls_logits, (list, tuple)) and len(old_cls_logits) == len(self.tasks)
         assert isinstance(cls_logits, list) and isinstance(reg_preds, list)
         assert len(cls_logits) == len(reg_preds) == len(self.tasks)
         assert preds_2d is not None and img_metas is not None, "the hybrid assignment needs preds_2d and img_metas[b]['lidar2img']"
@@ -812,15 +886,24 @@ class FrustumClusterHead(SparseClusterHeadV2):
         for i in range(len(self.tasks)):
             all_task_losses.update(self.loss_single_task(i, cls_logits[i], reg_preds[i], cluster_xyz, cluster_inds, no_aug_gt_bboxes_3d,
                                                          no_aug_gt_labels_3d, gt_bboxes_3d, gt_labels_3d, preds_2d, img_metas,
-                                                         fused=fused, lidar2img=lidar2img))
+                                                         old_cls_logits=old_cls_logits[i] if self._with_dist() else None,
+                                                         fused=fused, lidar2img=lidar2img,
+                                                         boxes_2d_pack=(boxes_2d_packs or {}).get(i)))
         return all_task_losses
 
     def get_targets(self, num_task_classes, no_aug_gt_bboxes_3d, no_aug_gt_labels_3d, gt_bboxes_3d, gt_labels_3d, preds_2d, cluster_xyz,
                     cluster_inds, task_id=None, img_metas_list=None, reg_preds=None, new_cls_logits=None, old_cls_logits=None,
-                    old_reg_preds=None, fused=True, lidar2img=None):
+                    old_reg_preds=None, fused=True, lidar2img=None, boxes_2d_pack=None):
         """:267-462 — (labels, label_weights, bbox_targets, bbox_weights, iou_labels = None) for GT already in the task's order
-        (`modify_gt_for_single_task`, both lists), and `task_info[str(task_id)]` = the four log scalars (totals over the batch)."""
+        (`modify_gt_for_single_task`, both lists), and `task_info[str(task_id)]` = the four log scalars (totals over the batch).
+        With a `FrustumAssigner` the assignment is K38's (`old_cls_logits`: the previous stage's logits of this task) and
+        `_last_assignment` also holds `source` (per query) and `source_counts` i64 [4] (none, 3-D, 2-D, distance)."""
         self._check_loss_cfg()
+        frustum = type(self.assigner) is FrustumAssigner
+        with_dist = self._with_dist()
+        if with_dist and old_cls_logits is None:
+            raise ValueError("FrustumClusterHead.get_targets: a FrustumAssigner with an assigner_dist needs old_cls_logits")
+        source = None
         batch_idx = cluster_inds if cluster_inds.ndim == 1 else cluster_inds[:, self.BATCH_COL]
         a = self.assigner
         on_device = fused and cluster_xyz.is_cuda and cluster_xyz.dtype == torch.float32
@@ -830,30 +913,58 @@ class FrustumClusterHead(SparseClusterHeadV2):
             from .... import hip_ops_assign
 
             dev = cluster_xyz.device
-            ptr_2d, rows_2d, labels_2d = pack_gt_for_device(no_aug_gt_bboxes_3d, no_aug_gt_labels_3d, dev, cols=7)
-            boxes_2d, keep = hip_ops_assign.gt_boxes_2d(rows_2d, labels_2d, ptr_2d, lidar2img.to(dev))
+            if boxes_2d_pack is not None:
+                ptr_2d, boxes_2d, keep = boxes_2d_pack
+            else:
+                ptr_2d, rows_2d, labels_2d = pack_gt_for_device(no_aug_gt_bboxes_3d, no_aug_gt_labels_3d, dev, cols=7)
+                boxes_2d, keep = hip_ops_assign.gt_boxes_2d(rows_2d, labels_2d, ptr_2d, lidar2img.to(dev))
             box_ptr, boxes, box_labels = pack_gt_for_device(gt_bboxes_3d, gt_labels_3d, dev, cols=None)
-            labels, bbox_targets, bbox_weights, assigned, stats = hip_ops_assign.hybrid_assign(
-                cluster_xyz, batch_idx, preds_2d.float(), ptr_2d, boxes_2d, keep, box_ptr, boxes, box_labels, num_task_classes,
-                self.box_code_size, a.assigner_3d.extra_height or 0.0, a.assigner_2d.pos_iou_thr, a.assigner_2d.min_pos_iou)
+            if frustum:
+                from .... import hip_ops_frustum
+
+                labels, bbox_targets, bbox_weights, assigned, source, stats = hip_ops_frustum.frustum_assign(
+                    cluster_xyz, batch_idx, preds_2d.float(), ptr_2d, boxes_2d, keep, box_ptr, boxes, box_labels, num_task_classes,
+                    self.box_code_size, a.assigner_3d.extra_height or 0.0, a.assigner_2d.pos_iou_thr, a.assigner_2d.min_pos_iou,
+                    old_cls_logits.detach().float() if with_dist else None,
+                    self._dist_table(num_task_classes, dev) if with_dist else None)
+            else:
+                labels, bbox_targets, bbox_weights, assigned, stats = hip_ops_assign.hybrid_assign(
+                    cluster_xyz, batch_idx, preds_2d.float(), ptr_2d, boxes_2d, keep, box_ptr, boxes, box_labels, num_task_classes,
+                    self.box_code_size, a.assigner_3d.extra_height or 0.0, a.assigner_2d.pos_iou_thr, a.assigner_2d.min_pos_iou)
             label_weights = cluster_xyz.new_ones(cluster_xyz.size(0))
+        elif frustum:
+            *out, parts = frustum_targets_host(
+                a, cluster_xyz, batch_idx, preds_2d, no_aug_gt_bboxes_3d, no_aug_gt_labels_3d, gt_bboxes_3d, gt_labels_3d, lidar2img,
+                num_task_classes, self.box_code_size, old_cls_logits if with_dist else None, return_parts=True)
+            labels, label_weights, bbox_targets, bbox_weights, assigned, stats = out
+            source = torch.zeros((cluster_xyz.size(0),), dtype=torch.int32)
+            for b, part in enumerate(parts):
+                if part is not None:
+                    source[torch.nonzero(batch_idx.cpu() == b, as_tuple=False).reshape(-1)] = part["source"].int()
+            source = source.to(cluster_xyz.device)
         else:
             labels, label_weights, bbox_targets, bbox_weights, assigned, stats = hybrid_targets_host(
                 a, cluster_xyz, batch_idx, preds_2d, no_aug_gt_bboxes_3d, no_aug_gt_labels_3d, gt_bboxes_3d, gt_labels_3d, lidar2img,
                 num_task_classes, self.box_code_size)
         self.task_info[str(task_id)] = dict(num_preds=stats[0], num_pos_preds=stats[1], num_gts=stats[2], assigned_gts=stats[3])
         self._last_assignment = dict(assigned=assigned, avg_factors=stats[4:6])
+        if source is not None:
+            self._last_assignment.update(source=source, source_counts=(source[:, None] == self._source_ids(source.device)[None, :]).sum(0))
         return labels, label_weights, bbox_targets, bbox_weights, None
 
     def loss_single_task(self, task_id, cls_logits, reg_preds, cluster_xyz, cluster_inds, no_aug_gt_bboxes_3d, no_aug_gt_labels_3d,
                          gt_bboxes_3d, gt_labels_3d, preds_2d, img_metas, iou_logits=None, old_cls_logits=None, old_reg_preds=None,
-                         fused=True, lidar2img=None):
+                         fused=True, lidar2img=None, boxes_2d_pack=None):
         """:138-265.  The LiDAR-query head's losses (`SparseClusterHeadV2.loss_single_task`) on the hybrid assignment's targets."""
-        no_aug = self.modify_gt_for_single_task(no_aug_gt_bboxes_3d, no_aug_gt_labels_3d, task_id)
+        this_task = task_id
 
         def targets(num_task_classes, xyz, batch_idx, gt_b, gt_l, reg_preds=None, task_id=None, fused=True):
+            # the un-augmented GT is read only to project it (K37a): a pack handed in already holds that, regrouped once by its maker
+            pack_used = boxes_2d_pack is not None and fused and xyz.is_cuda and xyz.dtype == torch.float32
+            no_aug = (None, None) if pack_used else self.modify_gt_for_single_task(no_aug_gt_bboxes_3d, no_aug_gt_labels_3d, this_task)
             return self.get_targets(num_task_classes, no_aug[0], no_aug[1], gt_b, gt_l, preds_2d, xyz, batch_idx, task_id=task_id,
-                                    img_metas_list=img_metas, reg_preds=reg_preds, fused=fused, lidar2img=lidar2img)
+                                    img_metas_list=img_metas, reg_preds=reg_preds, old_cls_logits=old_cls_logits, fused=fused,
+                                    lidar2img=lidar2img, boxes_2d_pack=boxes_2d_pack)
 
         return self._loss_single_task_with(targets, task_id, cls_logits, reg_preds, cluster_xyz, cluster_inds, gt_bboxes_3d, gt_labels_3d,
                                            fused)

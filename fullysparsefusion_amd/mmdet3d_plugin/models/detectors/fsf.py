@@ -992,27 +992,40 @@ class FSF(SingleStageFSD):
         return [merge_aug_bboxes_3d_device(boxes, scores.float(), labels, pass_idx, metas, cfg, len(head.class_names))]
 
     def multi_stage_refine_graph(self, obj_centers, obj_coors, obj_result, points, point_infos, pts_feat, batch_idx, mask_data,
-                                 mask_anno, img_metas, res_query_feat):
-        """`multi_stage_refine_train` (:905-959) without the per-stage `frustum_refined_head[i].loss(...)`: every stage's RoIs are
-        the boxes decoded from the previous stage's regression output (`decode_stage_bboxes`, no assigner in between — upstream has
-        none either), points pooled per RoI, the stage's refine SIR layers, `lidar_img_mlp` / `position_encoder` / `out_proj`, the
-        refined head.  Returns [(obj_centers, obj_result, query_feat)] per stage."""
+                                 mask_anno, img_metas, res_query_feat, stage_loss=None):
+        """`multi_stage_refine_train` (:905-959): every stage's RoIs are the boxes decoded from the previous stage's regression output
+        (`decode_stage_bboxes`, no assigner in between — upstream has none either), points pooled per RoI, the stage's refine SIR
+        layers, `lidar_img_mlp` / `position_encoder` / `out_proj`, the refined head.  `stage_loss(i_stage, obj_centers, obj_result,
+        old_obj_result)`, when given, runs right after each stage as upstream's `frustum_refined_head[i].loss(...)` does (:940-954).
+        Returns [(obj_centers, obj_result, query_feat, old_obj_result)] per stage: old_obj_result is the result the stage started
+        from (stage 0: `combine_frustum_and_fsd`'s), whose class logits the stage's distance assignment reads."""
         stages = []
         for i_stage in range(self.num_extra_stages):
+            old_obj_result = obj_result
             obj_centers, obj_result, res_query_feat = self.each_stage_refine(
                 i_stage, obj_centers, obj_coors, obj_result, points, point_infos, pts_feat, batch_idx, mask_data, mask_anno,
                 img_metas, res_query_feat)
-            stages.append((obj_centers, obj_result, res_query_feat))
+            if stage_loss is not None:
+                stage_loss(i_stage, obj_centers, obj_result, old_obj_result)
+            stages.append((obj_centers, obj_result, res_query_feat, old_obj_result))
         return stages
 
+    @staticmethod
+    def _same_2d_projection(a, b):
+        """Do heads a and b project the same regrouped un-augmented GT into the same cameras (one K37a pack serves both)?"""
+        names = lambda h: [list(t["class_names"]) for t in h.tasks]  # noqa: E731
+        return (a is b or (names(a) == names(b) and list(a.class_names) == list(b.class_names)
+                           and getattr(a.assigner, "num_cams", None) == getattr(b.assigner, "num_cams", None)))
+
     def forward_train_graph(self, points, img_metas, mask_data, mask_anno, gt_bboxes_3d=None, gt_labels_3d=None,
-                            lidar_head_losses=False, camera_head_losses=False, no_aug_gt_bboxes_3d=None, no_aug_gt_labels_3d=None):
+                            lidar_head_losses=False, camera_head_losses=False, no_aug_gt_bboxes_3d=None, no_aug_gt_labels_3d=None,
+                            refine_head_losses=False):
         """The differentiable graph of `forward_train` (:806-903) — segmentor + image fusion + segmentation head, camera queries
         WITH `frustum_obj_head`, LiDAR queries WITH `bbox_head`, `combine_frustum_and_fsd` (both `combine_*_mlp`), and
         `multi_stage_refine_train` (:905-959: RoI point pooling, `refine_sir_layers`, `lidar_img_mlp`, `position_encoder`,
-        `out_proj`, `frustum_refined_head`) — up to the tensors the losses would consume.  The camera head's and the refine stages'
-        target assignment and losses (`*.loss(...)`) are not built; a caller without them supplies a scalar
-        of these outputs (bench.py::dummy_loss: their sum, SURVEY §8(d) config 3).
+        `out_proj`, `frustum_refined_head`) — up to the tensors the losses consume.  Every head's target assignment and losses
+        (`*.loss(...)`) are behind the flags below; a caller without them supplies a scalar of these outputs (bench.py::dummy_loss:
+        their sum).
 
         With `gt_bboxes_3d` / `gt_labels_3d` (per sample: LiDARInstance3DBoxes or [M, >=7] tensors, and labels) the segmentation
         head's losses (`segmentor_feat_inhance_train`, :730-770) are added as out["losses"] = dict(loss_sem_seg, loss_vote), on the
@@ -1025,12 +1038,20 @@ class FSF(SingleStageFSD):
         `camera_head_losses=True` (needs the GT and the un-augmented GT `no_aug_gt_bboxes_3d` / `no_aug_gt_labels_3d`: the images are
         never augmented, so the 2-D half of the hybrid assignment projects the un-augmented boxes) also adds the camera-query head's
         losses and log scalars, `frustum_obj_head.loss(...)` on `frustum_obj_result` / `frustum_obj_centers` / `frustum_obj_coors` /
-        `frustum_preds_2d` (:847-860), under `frustum_<name><class names>`, on the device with no host wait (K37)."""
-        if camera_head_losses:
+        `frustum_preds_2d` (:847-860), under `frustum_<name><class names>`, on the device with no host wait (K37).
+
+        `refine_head_losses=True` (needs the same four GT arguments) also adds every refine stage's losses and log scalars,
+        `frustum_refined_head[i].loss(...)` on the stage's result, centres, `obj_coors`, `preds_2d` and the PREVIOUS stage's result
+        (:940-958), under `stage_<i>_<name><class names>`, on the device with no host wait (K38).  With `camera_head_losses` as well the
+        un-augmented GT is projected into the cameras once per task (K37a) and both heads read that pack; with one flag alone each head
+        projects it itself."""
+        for flag, on in (("camera_head_losses", camera_head_losses), ("refine_head_losses", refine_head_losses)):
+            if not on:
+                continue
             for name, value in (("gt_bboxes_3d", gt_bboxes_3d), ("gt_labels_3d", gt_labels_3d),
                                 ("no_aug_gt_bboxes_3d", no_aug_gt_bboxes_3d), ("no_aug_gt_labels_3d", no_aug_gt_labels_3d)):
                 if value is None:
-                    raise ValueError(f"forward_train_graph(camera_head_losses=True) needs {name}"
+                    raise ValueError(f"forward_train_graph({flag}=True) needs {name}"
                                      + (": the images are not augmented, the augmented boxes cannot stand in" if "no_aug" in name else ""))
         self._gather_cache = None
         self._fg_cache = None
@@ -1044,6 +1065,7 @@ class FSF(SingleStageFSD):
                                                                                   img_metas, cluster_center=None)
         l_feats, l_centers, l_coors, l_result = self.fsd_forward(seg_out_dict, img_metas)
         seg_losses = None
+        packs_head, packs = None, None
         if gt_bboxes_3d is not None:
             # The reference computes the targets on the input points and then keeps the rows of valid_pts_mask; the targets are
             # per-point functions of xyz and the sample's boxes, so computing them on the kept rows (seg_points, batch_idx), in
@@ -1056,10 +1078,19 @@ class FSF(SingleStageFSD):
                 fsd_losses = self.bbox_head.loss(l_result["cls_logits"], l_result["reg_preds"], l_centers, l_coors, gt_bboxes_3d,
                                                  gt_labels_3d, img_metas, iou_logits=l_result.get("iou_logits", None))
                 seg_losses.update({"fsd_" + k: v for k, v in fsd_losses.items()})
+            if (camera_head_losses and refine_head_losses and self.num_extra_stages > 0 and f_centers.is_cuda
+                    and f_centers.dtype == torch.float32 and hasattr(self.frustum_obj_head.assigner, "num_cams")):
+                # both flags: K37a once per task and step, every head that projects the same GT into the same cameras reads this
+                # pack.  With one flag alone the head runs K37a itself, as it did before there was a pack.
+                packs_head = self.frustum_obj_head
+                l2i = packs_head._lidar2img_batch(img_metas, f_centers.device)
+                packs = {t: packs_head.gt_boxes_2d_pack(t, no_aug_gt_bboxes_3d, no_aug_gt_labels_3d, l2i, f_centers.device)
+                         for t in range(len(packs_head.tasks))}
             if camera_head_losses:
                 frustum_losses = self.frustum_obj_head.loss(
                     f_result["cls_logits"], f_result["reg_preds"], f_centers, f_coors, no_aug_gt_bboxes_3d, no_aug_gt_labels_3d,
-                    gt_bboxes_3d, gt_labels_3d, f_preds_2d, img_metas, iou_logits=f_result.get("iou_logits", None))
+                    gt_bboxes_3d, gt_labels_3d, f_preds_2d, img_metas, iou_logits=f_result.get("iou_logits", None),
+                    boxes_2d_packs=packs)
                 seg_losses.update({"frustum_" + k: v for k, v in frustum_losses.items()})
         elif lidar_head_losses:
             raise ValueError("forward_train_graph(lidar_head_losses=True) needs gt_bboxes_3d and gt_labels_3d")
@@ -1072,23 +1103,66 @@ class FSF(SingleStageFSD):
         if seg_losses is not None:
             out["losses"] = seg_losses
         if self.num_extra_stages > 0:
+            stage_loss = None
+            if refine_head_losses:
+                def stage_loss(i_stage, centers, result, old_result):
+                    head = self.frustum_refined_head[i_stage]
+                    shared = packs if packs is not None and self._same_2d_projection(packs_head, head) else None
+                    losses = head.loss(result["cls_logits"], result["reg_preds"], centers, obj_coors, no_aug_gt_bboxes_3d,
+                                       no_aug_gt_labels_3d, gt_bboxes_3d, gt_labels_3d, preds_2d, img_metas,
+                                       result.get("iou_logits", None), old_result["cls_logits"], old_result["reg_preds"],
+                                       boxes_2d_packs=shared)
+                    seg_losses.update({f"stage_{i_stage}_" + k: v for k, v in losses.items()})
+
             stages = self.multi_stage_refine_graph(obj_centers, obj_coors, obj_result, seg_out_dict["seg_points"], point_infos,
                                                    seg_out_dict["seg_feats"], seg_out_dict["batch_idx"], mask_data, mask_anno,
-                                                   img_metas, obj_feats)
+                                                   img_metas, obj_feats, stage_loss=stage_loss)
             out["stage_results"] = [s[1] for s in stages]
             out["stage_centers"] = [s[0] for s in stages]
         self._gather_cache = None
         clear_unique_cache()
         return out
 
-    def forward_train(self, points, img_metas, *args, mask_data=None, mask_anno=None, **kwargs):
-        """`forward_train` (:806-903): the graph is `forward_train_graph`, which also closes the segmentation head (K35), the
-        LiDAR-query head (K36) and the camera-query head (K37) with their losses; the refine stages' `.loss(...)` (FrustumAssigner,
-        distance assigner) is not built, so the whole training step is not either."""
-        # (ADVICE r5: this used to run the whole graph and only then raise through `head.loss`)
-        raise NotImplementedError(
-            "FSF.forward_train: the refine stages' target assignment and losses (`frustum_refined_head.loss`: FrustumAssigner + DistAssigner, "
-            "FSF.py:806-903) are not built; `forward_train_graph(points, img_metas, mask_data, mask_anno)` "
-            "returns every tensor they would consume, with `gt_bboxes_3d=..., gt_labels_3d=...` also the segmentation head's losses, "
-            "with `lidar_head_losses=True` the LiDAR-query head's and with `camera_head_losses=True, no_aug_gt_bboxes_3d=..., "
-            "no_aug_gt_labels_3d=...` the camera-query head's (out['losses'])")
+    def forward_train(self, points, img_metas, no_aug_gt_bboxes_3d=None, no_aug_gt_labels_3d=None, gt_bboxes_3d=None, gt_labels_3d=None,
+                      mask_data=None, mask_anno=None, gt_bboxes_ignore=None, img=None):
+        """`forward_train` (:806-903): the reference's loss dict — the segmentation head's `loss_sem_seg` / `loss_vote` (K35), the
+        camera-query head's `frustum_*` (K37), the LiDAR-query head's `fsd_*` (K36) and every refine stage's `stage_<i>_*` (K38) — all
+        on the device with no host wait: `forward_train_graph` with its three flags.  Rows with label < 0 are dropped from both GT
+        lists first (:821-824) when the labels are on the host (boxes already on the device are filtered by an uploaded index list,
+        which does not wait); device-resident labels keep them, every consumer skips them (no shape then depends on device data).  A training step without ground truth is not built and is refused before anything runs."""
+        gt = (("no_aug_gt_bboxes_3d", no_aug_gt_bboxes_3d), ("no_aug_gt_labels_3d", no_aug_gt_labels_3d), ("gt_bboxes_3d", gt_bboxes_3d),
+              ("gt_labels_3d", gt_labels_3d))
+        missing = [name for name, value in gt if value is None]
+        if missing:
+            raise NotImplementedError(
+                f"FSF.forward_train: a training step without ground truth is not built (missing: {', '.join(missing)}); it needs "
+                "no_aug_gt_bboxes_3d, no_aug_gt_labels_3d, gt_bboxes_3d and gt_labels_3d, and is `forward_train_graph(points, img_metas, "
+                "mask_data, mask_anno, gt_bboxes_3d=..., gt_labels_3d=..., no_aug_gt_bboxes_3d=..., no_aug_gt_labels_3d=..., "
+                "lidar_head_losses=True, camera_head_losses=True, refine_head_losses=True)['losses']`; without those flags and "
+                "arguments the graph returns the tensors the losses would consume")
+        if mask_data is None or mask_anno is None:
+            raise ValueError("FSF.forward_train needs mask_data and mask_anno (the 2-D detector's instance masks and their annotations)")
+        from ..decode_heads.segmentation_head import gt_box_rows
+
+        def drop_unlabelled(boxes, labels):
+            out_b, out_l = [], []
+            for b, l in zip(boxes, labels):
+                l = torch.as_tensor(l)
+                if not l.is_cuda:
+                    kept = torch.nonzero(l.reshape(-1) >= 0).reshape(-1)  # (on the host: its length is known without a wait)
+                    rows = gt_box_rows(b)
+                    if rows.is_cuda:  # host labels with device boxes: the kept rows by index, a pinned upload instead of a mask
+                        rows = rows.index_select(0, kept.pin_memory().to(rows.device, non_blocking=True))
+                    else:
+                        rows = rows[kept]
+                    b, l = rows, l.reshape(-1)[kept]
+                out_b.append(b)
+                out_l.append(l)
+            return out_b, out_l
+
+        no_aug_gt_bboxes_3d, no_aug_gt_labels_3d = drop_unlabelled(no_aug_gt_bboxes_3d, no_aug_gt_labels_3d)
+        gt_bboxes_3d, gt_labels_3d = drop_unlabelled(gt_bboxes_3d, gt_labels_3d)
+        out = self.forward_train_graph(points, img_metas, mask_data, mask_anno, gt_bboxes_3d=gt_bboxes_3d, gt_labels_3d=gt_labels_3d,
+                                       lidar_head_losses=True, camera_head_losses=True, no_aug_gt_bboxes_3d=no_aug_gt_bboxes_3d,
+                                       no_aug_gt_labels_3d=no_aug_gt_labels_3d, refine_head_losses=True)
+        return out["losses"]

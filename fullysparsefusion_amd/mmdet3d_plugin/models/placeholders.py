@@ -1,11 +1,11 @@
 """Config `type=` names that are OUT OF SCOPE of the hot path (unused head variants, label
 assigners, losses other than models/losses.py's, dataset classes and hooks) resolve to ONE generic stand-in, so that
 `projects/configs/nuScenes/FSF_nuScenes_config.py` loads and the model builds; using one raises, naming what is missing.
-Nothing here computes anything (no silent fallbacks).  `HybridAssigner`, `PointInBoxAssigner` and `MaxIoUAssigner` are real
-(core/assigners.py, K37); `FrustumAssigner` and `DistAssigner`, the refine heads', stay stand-ins."""
+Nothing here computes anything (no silent fallbacks).  Every label assigner the FSF configs name is real (core/assigners.py):
+`HybridAssigner`, `PointInBoxAssigner` and `MaxIoUAssigner` (K37), `FrustumAssigner` and `DistAssigner`, the refine heads' (K38)."""
 import torch.nn as nn
 
-from ..registry import BBOX_ASSIGNERS, BBOX_CODERS, DATASETS, HOOKS, MODELS, PIPELINES
+from ..registry import BBOX_CODERS, DATASETS, HOOKS, MODELS, PIPELINES
 
 
 def out_of_scope(name, where, module=False):
@@ -26,7 +26,6 @@ for _reg, _where, _module, _names in (
         (MODELS, "heads / losses of the training path", True,
          "MultiStageRefineHead GroupCorrectionHead SmoothL1Loss"),
         (BBOX_CODERS, "core/bbox/coders", False, "ABSPointBBoxCoder"),
-        (BBOX_ASSIGNERS, "core/bbox/assigners", False, "FrustumAssigner DistAssigner"),
         (PIPELINES, "datasets/pipelines (training augmentations)", False,
          "MyLoadPointsFromMultiSweeps LoadAnnotations3D ObjectSample ObjectRangeFilter ObjectNameFilter PointShuffle MyObjectSample "
          "MyObjectRangeFilter MyRandomFlip3D MyPointShuffle"),

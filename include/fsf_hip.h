@@ -601,6 +601,35 @@ int fsf_hybrid_assign(const float* cluster_xyz, int64_t n, int64_t xyz_stride, c
                       void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * K38  refine-stage head targets: frustum (3-D / 2-D) + distance assignment (docs/kernels/K38_frustum_assign.md)
+ * Replaces FrustumAssigner.assign (projects/mmdet3d_plugin/core/bbox/assigners/frustum_assigner.py: HybridAssigner's two steps, then
+ *   assigner_dist merged into the entries they left <= 0) and DistAssigner.assign / assign_by_dist_single / combine_assign_result
+ *   (core/bbox/assigners/dist_assigner.py), under FrustumClusterHead.get_targets (models/dense_heads/frustum_cluster_head.py:267-462)
+ *   as the refine stages call it (models/detectors/FSF.py:940-954).  The losses are K36b / K36c on these targets.
+ * fsf_frustum_assign: K37b's four launches; the distance step runs inside the per-query kernel.  Every argument up to min_pos_iou and
+ *   every output is fsf_hybrid_assign's.  No synchronisation, no float atomics, no memset; two runs are bit-identical.
+ *   old_cls_logits  f32 rows of logits_stride (>= num_classes) floats: the PREVIOUS stage's class logits of query i for this task
+ *   class_max_dist  f32 [num_classes] device: the radius of each class; <= 0: the class never assigns.  NULL: no distance step, every
+ *                   output equals fsf_hybrid_assign's bit for bit (old_cls_logits is then not read and may be NULL)
+ *   source          i32 [n] or NULL: which step assigned query i: 0 none, 1 3-D containment, 2 2-D IoU, 3 distance
+ *   A query that neither step assigned takes class c = the first maximum of its num_classes logits (strict > from column 0; a row of
+ *   NaN gives 0), then among the rows of its sample with box_labels == c the first row of minimum d, and is assigned that row iff
+ *   d < class_max_dist[c];  d = sqrt_rn(fl(fl(dx dx) + fl(dy dy))), dx = qx - gx, dy = qy - gy in f32, no fma.  A NaN or infinite d
+ *   never wins.  Label, encoded target, weights (the copy-paste flag included), box_hit and stats then follow as in K37b.
+ *   Returns FSF_ERR_INVALID_ARG for a table with logits_stride < num_classes or (n > 0) without old_cls_logits.
+ *   workspace: fsf_frustum_assign_workspace_bytes(num_boxes, num_boxes_2d, ncam, n) (= fsf_hybrid_assign_workspace_bytes)
+ */
+int64_t fsf_frustum_assign_workspace_bytes(int64_t num_boxes, int64_t num_boxes_2d, int32_t ncam, int64_t n);
+int fsf_frustum_assign(const float* cluster_xyz, int64_t n, int64_t xyz_stride, const void* batch_idx, int32_t batch_idx_bytes,
+                       int64_t batch_stride, const float* preds_2d, int64_t preds_stride, const int32_t* box_ptr_2d, const float* boxes_2d,
+                       const int32_t* keep_2d, int64_t num_boxes_2d, int32_t ncam, const int32_t* box_ptr, int32_t num_samples,
+                       const float* boxes, int64_t num_boxes, int64_t box_stride, int32_t box_cols, const int32_t* box_labels,
+                       int32_t num_classes, int32_t code_size, float extra_height, float pos_iou_thr, float min_pos_iou,
+                       const float* old_cls_logits, int64_t logits_stride, const float* class_max_dist, void* workspace,
+                       int64_t workspace_bytes, int64_t* labels, float* bbox_targets, float* bbox_weights, int32_t* assigned,
+                       int32_t* source, float* stats, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * K13-K15  LiDAR -> camera projection + per-point instance-mask gather
  * Replaces: FSF.prj_points_2d (projects/mmdet3d_plugin/models/detectors/FSF.py:169-200) and
  *   FSF.points_in_mask (:202-226) for one batch sample; the caller loops samples like frustum_gather (:228-258).
