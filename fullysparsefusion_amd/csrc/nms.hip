@@ -12,6 +12,7 @@
 //   (moved into B's frame) against B's four sides (Sutherland-Hodgman) — no intersection-point sort, no degenerate
 //   cases — which gives the same area as upstream's intersect-and-sort polygon up to fp32 rounding.
 #include "common.h"
+#include "bev_overlap.h"  // rect_overlap_rotated / rect_overlap_normal / iou_bev (also compiled for the host by the tests)
 
 namespace fsf {
 
@@ -44,76 +45,6 @@ struct NmsBuildArgs {
   int64_t rows;
   int cwords, csum_words;
 };
-
-__device__ __forceinline__ float rect_overlap_rotated(const float* a, const float* b) {
-  // B frame: origin at B's centre, axes along B's sides
-  const float bcx = 0.5f * (b[0] + b[2]), bcy = 0.5f * (b[1] + b[3]);
-  const float bhx = 0.5f * (b[2] - b[0]), bhy = 0.5f * (b[3] - b[1]);
-  const float acx = 0.5f * (a[0] + a[2]), acy = 0.5f * (a[1] + a[3]);
-  const float ahx = 0.5f * (a[2] - a[0]), ahy = 0.5f * (a[3] - a[1]);
-  if (!(bhx > 0.f) || !(bhy > 0.f) || !(ahx > 0.f) || !(ahy > 0.f)) return 0.f;
-  const float ca = cosf(a[4]), sa = sinf(a[4]), cb = cosf(b[4]), sb = sinf(b[4]);
-  // Upstream's corner rotation (iou3d rotate_around_center, the mmdet3d 0.x yaw sense, the same one K17's
-  // lidar_to_local_coords implies): corner = centre + M(yaw) * offset with M = [[cos, sin], [-sin, cos]].
-  // Polygon = A's corners in the world, then into B's frame with M(yaw_b)^T.
-  float px[8], py[8], qx[8], qy[8];
-  const float ox[4] = {-ahx, ahx, ahx, -ahx}, oy[4] = {-ahy, -ahy, ahy, ahy};
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    const float wx = acx + ca * ox[k] + sa * oy[k] - bcx;
-    const float wy = acy - sa * ox[k] + ca * oy[k] - bcy;
-    px[k] = cb * wx - sb * wy;
-    py[k] = sb * wx + cb * wy;
-  }
-  int n = 4;
-  // clip against x <= bhx, x >= -bhx, y <= bhy, y >= -bhy
-#pragma unroll
-  for (int side = 0; side < 4; ++side) {
-    const float lim = (side < 2) ? bhx : bhy;
-    const float sgn = (side & 1) ? -1.f : 1.f;
-    int m = 0;
-    for (int k = 0; k < n; ++k) {
-      const int k2 = (k + 1 == n) ? 0 : k + 1;
-      const float c0 = sgn * ((side < 2) ? px[k] : py[k]);
-      const float c1 = sgn * ((side < 2) ? px[k2] : py[k2]);
-      const bool in0 = c0 <= lim, in1 = c1 <= lim;
-      if (in0) {
-        qx[m] = px[k];
-        qy[m] = py[k];
-        ++m;
-      }
-      if (in0 != in1) {
-        const float t = (lim - c0) / (c1 - c0);
-        qx[m] = px[k] + t * (px[k2] - px[k]);
-        qy[m] = py[k] + t * (py[k2] - py[k]);
-        ++m;
-      }
-    }
-    n = m;
-    for (int k = 0; k < n; ++k) {
-      px[k] = qx[k];
-      py[k] = qy[k];
-    }
-    if (n < 3) return 0.f;
-  }
-  float area = 0.f;
-  for (int k = 1; k + 1 < n; ++k)
-    area += (px[k] - px[0]) * (py[k + 1] - py[0]) - (px[k + 1] - px[0]) * (py[k] - py[0]);
-  return 0.5f * fabsf(area);
-}
-
-__device__ __forceinline__ float rect_overlap_normal(const float* a, const float* b) {
-  const float l = fmaxf(a[0], b[0]), r = fminf(a[2], b[2]);
-  const float t = fmaxf(a[1], b[1]), d = fminf(a[3], b[3]);
-  return fmaxf(r - l, 0.f) * fmaxf(d - t, 0.f);
-}
-
-__device__ __forceinline__ float iou_bev(const float* a, const float* b, int rotated) {
-  const float sa = (a[2] - a[0]) * (a[3] - a[1]);
-  const float sb = (b[2] - b[0]) * (b[3] - b[1]);
-  const float ov = rotated ? rect_overlap_rotated(a, b) : rect_overlap_normal(a, b);
-  return ov / fmaxf(sa + sb - ov, 1e-8f);
-}
 
 // block (col word, row block): thread = row box, tests it against the 64 boxes of the column word.  A pair whose
 // circumscribed circles do not touch cannot overlap: that test (5 flops) removes nearly every pair of a real scene

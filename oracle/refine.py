@@ -95,10 +95,17 @@ def _inside(poly, p, eps=1e-9):
     return True
 
 
+# Two edges count as parallel when the sine of their angle is below this.  The cross product of two exactly collinear 10 m edges
+# comes out as ~1e-14 in float64, not 0: an absolute test alone let such a pair "intersect" at a meaningless parameter and put a point
+# of one box's side, outside the other box, into the polygon (two boxes sharing an edge: a quarter of a box instead of 0).  Collinear
+# edges add nothing the contained-corner candidates do not already hold.
+PARALLEL_REL = 1e-12
+
+
 def _seg_intersection(p0, p1, q0, q1):
     d1, d2 = p1 - p0, q1 - q0
     den = d1[0] * d2[1] - d1[1] * d2[0]
-    if abs(den) < 1e-14:
+    if abs(den) < max(1e-14, PARALLEL_REL * np.hypot(d1[0], d1[1]) * np.hypot(d2[0], d2[1])):
         return None
     t = ((q0[0] - p0[0]) * d2[1] - (q0[1] - p0[1]) * d2[0]) / den
     u = ((q0[0] - p0[0]) * d1[1] - (q0[1] - p0[1]) * d1[0]) / den
@@ -155,11 +162,17 @@ def rotated_overlap_batch(a, b):
     intersections + the 8 contained corners as a masked candidate list, angular sort around the centroid of the valid
     ones, shoelace.  Checked against the scalar function in tests/test_oracle_golden.py."""
     b = np.asarray(b, dtype=np.float64).reshape(-1, 5)
+    return rotated_overlap_pairs(np.broadcast_to(np.asarray(a, dtype=np.float64).reshape(1, 5), b.shape), b)
+
+
+def rotated_overlap_pairs(a, b):
+    """`rotated_overlap(a[k], b[k])` for every row pair of a, b [m, 5] (the body of `rotated_overlap_batch`)."""
+    a = np.asarray(a, dtype=np.float64).reshape(-1, 5)
+    b = np.asarray(b, dtype=np.float64).reshape(-1, 5)
     m = b.shape[0]
     if m == 0:
         return np.zeros(0)
-    pb = _corners_batch(b)
-    pa = np.broadcast_to(_corners(a)[None], (m, 4, 2))
+    pa, pb = _corners_batch(a), _corners_batch(b)
     cand = np.zeros((m, 24, 2))
     valid = np.zeros((m, 24), dtype=bool)
     k = 0
@@ -170,7 +183,7 @@ def rotated_overlap_batch(a, b):
             q0, q1 = pb[:, j], pb[:, (j + 1) % 4]
             d2 = q1 - q0
             den = d1[:, 0] * d2[:, 1] - d1[:, 1] * d2[:, 0]
-            ok = np.abs(den) >= 1e-14
+            ok = np.abs(den) >= np.maximum(1e-14, PARALLEL_REL * np.hypot(d1[:, 0], d1[:, 1]) * np.hypot(d2[:, 0], d2[:, 1]))
             sden = np.where(ok, den, 1.0)
             t = ((q0[:, 0] - p0[:, 0]) * d2[:, 1] - (q0[:, 1] - p0[:, 1]) * d2[:, 0]) / sden
             u = ((q0[:, 0] - p0[:, 0]) * d1[:, 1] - (q0[:, 1] - p0[:, 1]) * d1[:, 0]) / sden
