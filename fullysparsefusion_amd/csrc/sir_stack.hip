@@ -11,12 +11,19 @@
 // interpreter is the bound (profiles/r6_host_gaps_config2_1sweep.txt).  Here the same entry points are called back to back from C++ with
 // the arguments the Python path passes: bit-identical results (tests/test_sir_stack_gpu.py).
 //
+// A block's first two launches — K21 and the first K22s layer — run as ONE where fsf_sir_input_linear_segmax (csrc/sir_linear.hip) takes the
+// shape and FSF_OPT_SIR_FUSED is set: the same bits, the K21 output never written (tests/test_sir_fused_gpu.py).
+//
 // Memory: ONE arena from the caller (fsf_sir_stack_arena_bytes): the K21 output of the current block, two row buffers the layers
 // alternate between, two group tables.  The group features land in the caller's [groups, sum of layer widths] table (pre-filled with
 // -inf), the last layer's rows in `rows_out` when the caller wants them.  Nothing is allocated or freed here.
 #include <algorithm>
 
 #include "common.h"
+
+namespace fsf {
+extern std::atomic<int64_t> g_opt_sir_fused;  // status.hip (fsf_set_option(FSF_OPT_SIR_FUSED))
+}
 
 static inline int64_t sst_pad4(int64_t c) { return (c + 3) / 4 * 4; }
 
@@ -75,6 +82,8 @@ extern "C" int fsf_sir_stack_forward(const FsfSirBlock* blocks, int32_t num_bloc
   const float* prev_rows = nullptr;  // the previous block's point rows [n, prev_c] (sorted order)
   int32_t prev_c = 0;
   int rsel = 0, tsel = 0;
+  const int64_t fused_opt = fsf::g_opt_sir_fused.load(std::memory_order_relaxed);  // (0 never / 1 from the row threshold / 2 always)
+  const bool use_fused = fused_opt >= 2 || (fused_opt == 1 && n >= FSF_SIR_FUSED_MIN_ROWS);
   for (int b = 0; b < num_blocks; ++b) {
     const FsfSirBlock& k = blocks[b];
     const int64_t cpad = sst_pad4(k.in_cols);
@@ -87,16 +96,36 @@ extern "C" int fsf_sir_stack_forward(const FsfSirBlock* blocks, int32_t num_bloc
       }
       if (p_cols + fcols + e_cols != k.in_cols) return FSF_ERR_INVALID_ARG;
     }
+    const float* prev_parts[1] = {prev_rows};
+    const int64_t prev_strides[1] = {prev_c};
+    const int32_t prev_cols[1] = {prev_c};
+    // ---- K21 + the first layer as ONE launch (csrc/sir_linear.hip: the same bits, the [n, in_cols] matrix never written) where the
+    // fused entry point takes the shape; FSF_ERR_UNSUPPORTED (or the option off, or a stack below the row threshold): the two calls
+    bool fused = false;
+    if (use_fused && k.layer[0].left_f16) {
+      const FsfSirLayer& L = k.layer[0];
+      const bool last_block = b == num_blocks - 1;
+      const bool want_rows = k.num_layers > 1 || !last_block || rows_out != nullptr;
+      float* out = !want_rows ? nullptr : (k.num_layers == 1 && last_block ? rows_out : rbuf[rsel]);
+      const int64_t so_stride = num_groups > 1 ? groups_stride : sst_pad4(L.c);
+      rc = fsf_sir_input_linear_segmax(points, points_stride, p_cols, k.xyz_normalizer, b == 0 ? feat_parts : prev_parts,
+                                       b == 0 ? feat_strides : prev_strides, b == 0 ? feat_cols : prev_cols, b == 0 ? num_parts : 1,
+                                       b == 0 ? feats_index : nullptr, b == 0 ? direct_parts_mask : 0, extra, extra_stride, e_cols, extra_div,
+                                       f_cluster, f_cluster_stride, r_cols, k.rel_div, k.w1, k.g1, k.b1, k.h1, k.w2, k.g2, k.b2, k.h2, k.w3, k.g3,
+                                       k.b3, k.mlp_eps, k.mlp_act, n, L.planes_left, L.c, L.bias, L.norm, L.gamma, L.beta, L.eps, L.act, seg_ids,
+                                       num_groups, groups + col, so_stride, out, L.c, stream);
+      if (rc == FSF_OK) fused = true;
+      else if (rc != FSF_ERR_UNSUPPORTED) return rc;
+    }
     // ---- K21: the block's input rows (SIRLayer.forward_sorted -> hip_ops.sir_input)
-    if (b == 0) {
+    if (fused) {
+      rc = FSF_OK;
+    } else if (b == 0) {
       rc = fsf_sir_input_gather(points, points_stride, p_cols, k.xyz_normalizer, feat_parts, feat_strides, feat_cols, num_parts, feats_index,
                                 direct_parts_mask, extra, extra_stride, e_cols, extra_div, f_cluster, f_cluster_stride, r_cols, k.rel_div, k.w1,
                                 k.g1, k.b1, k.h1, k.w2, k.g2, k.b2, k.h2, k.w3, k.g3, k.b3, k.mlp_eps, k.mlp_act, n, xbuf, cpad, stream);
     } else {
-      const float* parts[1] = {prev_rows};
-      const int64_t strides[1] = {prev_c};
-      const int32_t cols[1] = {prev_c};
-      rc = fsf_sir_input_gather(points, points_stride, p_cols, k.xyz_normalizer, parts, strides, cols, 1, nullptr, 0, extra, extra_stride, e_cols,
+      rc = fsf_sir_input_gather(points, points_stride, p_cols, k.xyz_normalizer, prev_parts, prev_strides, prev_cols, 1, nullptr, 0, extra, extra_stride, e_cols,
                                 extra_div, f_cluster, f_cluster_stride, r_cols, k.rel_div, k.w1, k.g1, k.b1, k.h1, k.w2, k.g2, k.b2, k.h2, k.w3,
                                 k.g3, k.b3, k.mlp_eps, k.mlp_act, n, xbuf, cpad, stream);
     }
@@ -112,6 +141,7 @@ extern "C" int fsf_sir_stack_forward(const FsfSirBlock* blocks, int32_t num_bloc
       float* out = !want_rows ? nullptr : (last_layer && last_block ? rows_out : rbuf[rsel]);
       float* seg_out = groups + col;
       const float* table = nullptr;
+      const bool done = i == 0 && fused;  // (layer 0 ran in the fused launch, into the same `out` and `seg_out`)
       if (i > 0) {  // (group W_right^T): the right half of cat([point, group[inv]], 1) W^T, once per group
         const float* g = groups + (col - x_cols);
         float* t = tbuf[tsel];
@@ -125,7 +155,9 @@ extern "C" int fsf_sir_stack_forward(const FsfSirBlock* blocks, int32_t num_bloc
         table = t;
       }
       const int64_t so_stride = num_groups > 1 ? groups_stride : sst_pad4(L.c);
-      if (L.left_f16)
+      if (done)
+        rc = FSF_OK;
+      else if (L.left_f16)
         rc = fsf_linear_f16w_norm_act_segmax(x, n, x_cols, x_stride, L.planes_left, L.c, L.bias, table, table ? seg_ids : nullptr, table ? L.c : 0,
                                              L.norm, L.gamma, L.beta, L.eps, L.act, seg_ids, num_groups, seg_out, so_stride, out, L.c, stream);
       else

@@ -24,11 +24,19 @@ std::atomic<int64_t> g_opt_pool_brute{[] {
   return (int64_t)(e ? atoll(e) : 0);
 }()};
 std::atomic<int64_t> g_host_waits{0};
+std::atomic<int64_t> g_opt_sir_fused{[] {
+  const char* e = getenv("FSF_SIR_FUSED");  // read once, when the library is loaded
+  return (int64_t)(e ? atoll(e) : FSF_SIR_FUSED_DEFAULT);
+}()};
 }  // namespace fsf
 
 extern "C" int fsf_set_option(int32_t option, int64_t value) {
   if (option == FSF_OPT_POOL_BRUTE) {
     fsf::g_opt_pool_brute.store(value, std::memory_order_relaxed);
+    return FSF_OK;
+  }
+  if (option == FSF_OPT_SIR_FUSED) {
+    fsf::g_opt_sir_fused.store(value, std::memory_order_relaxed);
     return FSF_OK;
   }
   return FSF_ERR_INVALID_ARG;
@@ -37,5 +45,6 @@ extern "C" int fsf_set_option(int32_t option, int64_t value) {
 extern "C" int64_t fsf_get_option(int32_t option) {
   if (option == FSF_OPT_POOL_BRUTE) return fsf::g_opt_pool_brute.load(std::memory_order_relaxed);
   if (option == FSF_OPT_HOST_WAITS) return fsf::g_host_waits.load(std::memory_order_relaxed);
+  if (option == FSF_OPT_SIR_FUSED) return fsf::g_opt_sir_fused.load(std::memory_order_relaxed);
   return -1;
 }

@@ -1409,6 +1409,7 @@ def linear_planes_norm_act(xp: RowPlanes, wplanes: torch.Tensor, out_features: i
 
 # ----------------------------------------------------------------------------------- refine-stage ops
 OPT_POOL_BRUTE = _lib.DEFINES["FSF_OPT_POOL_BRUTE"]
+OPT_SIR_FUSED = _lib.DEFINES["FSF_OPT_SIR_FUSED"]
 
 
 def set_option(option: int, value: int) -> int:
@@ -1833,10 +1834,11 @@ class SirStackDescriptor:
 
 
 def sir_stack_forward(desc: SirStackDescriptor, points, feats, f_cluster, seg_ids, groups, want_rows, extra=None, extra_div: float = 1.0,
-                      feats_index=None, direct_parts=()):
+                      feats_index=None, direct_parts=(), rows_out=None, arena=None):
     """fsf_sir_stack_forward (K31): every block of a SIR stack on rows sorted by group in ONE native call.  Arguments as
     `sir_input` takes them for the stack's first block (`feats`: tensor or up to three side by side, through `feats_index`), `seg_ids`
-    i64 [n] nondecreasing, `groups` f32 [m, sum of all layers' widths] holding -inf.  Returns the last layer's rows f32 [n, c] or None."""
+    i64 [n] nondecreasing, `groups` f32 [m, sum of all layers' widths] holding -inf.  Returns the last layer's rows f32 [n, c] or None.  `rows_out` (contiguous
+    f32 [n, c]) / `arena` (u8, 256-byte aligned, >= fsf_sir_stack_arena_bytes): the caller's buffers instead of fresh ones."""
     parts = list(feats) if isinstance(feats, (list, tuple)) else [feats]
     require_cuda(points, f_cluster, extra, feats_index, seg_ids, groups, *parts)
     n, m = points.size(0), groups.size(0)
@@ -1856,9 +1858,16 @@ def sir_stack_forward(desc: SirStackDescriptor, points, feats, f_cluster, seg_id
     fs = (ctypes.c_int64 * k)(*[int(st(t)) for t in parts])
     fc = (ctypes.c_int32 * k)(*[int(t.size(1)) for t in parts])
     h = _L()
+    if switches.SIR_FUSED is not None and bool(h.fsf_get_option(OPT_SIR_FUSED)) != bool(switches.SIR_FUSED):
+        check(h.fsf_set_option(OPT_SIR_FUSED, int(bool(switches.SIR_FUSED))), "fsf_set_option")
     nbytes = int(h.fsf_sir_stack_arena_bytes(desc.blocks, desc.num_blocks, n, m))
-    arena = torch.empty((nbytes,), dtype=torch.uint8, device=points.device)
-    rows = torch.empty((n, desc.widths[-1][-1]), dtype=torch.float32, device=points.device) if want_rows else None
+    if arena is None:
+        arena = torch.empty((nbytes,), dtype=torch.uint8, device=points.device)
+    assert arena.dtype == torch.uint8 and arena.is_contiguous() and arena.numel() >= nbytes and arena.data_ptr() % 256 == 0
+    rows = None
+    if want_rows:
+        rows = rows_out if rows_out is not None else torch.empty((n, desc.widths[-1][-1]), dtype=torch.float32, device=points.device)
+        assert rows.dtype == torch.float32 and rows.shape == (n, desc.widths[-1][-1]) and rows.is_contiguous()
     check(h.fsf_sir_stack_forward(desc.blocks, desc.num_blocks, rp(points), st(points), points.size(1), fp, fs, fc, k, ptr(feats_index), direct_mask,
                                   rp(extra), st(extra), extra.size(1) if extra is not None else 0, float(extra_div), rp(f_cluster), st(f_cluster),
                                   f_cluster.size(1), ptr(seg_ids), n, m, c_p(groups.data_ptr()), groups.stride(0) if m > 1 else groups.size(1),

@@ -26,6 +26,11 @@ REFINE_DIRECT = _on("FSF_REFINE_DIRECT")              # inference: the refine he
 K22F = _on("FSF_K22F")                                # the <= 128-channel-slice Linears on f16 x 3 (x split in the kernel); off: bf16 x 6
 K22H = _on("FSF_K22H")                                # the >= 256-wide Linears on f16 x 3 planes; off: K22 slices / the library
 
+# The library's own switch FSF_OPT_SIR_FUSED (fsf_set_option: K31 runs a block's K21 + first K22s layer as one launch, csrc/sir_linear.hip;
+# the same bits either way, so not one of the dispatch sites above).  The library reads FSF_SIR_FUSED itself when it is loaded; None here
+# = leave the library's setting alone, True / False = hip_ops.sir_stack_forward sets the option before its next call.
+SIR_FUSED = {None: None, "0": False}.get(os.environ.get("FSF_SIR_FUSED"), True)
+
 # ---- tuning constants (row counts from which a path pays; set once, measured in the round named) ----
 PLANES_MIN_ROWS = 4096            # K9d from this many output rows (round 2)
 K22H_MIN_ROWS = 1024              # K22h from this many rows (round 5)

@@ -47,9 +47,15 @@ int fsf_abi_version(void);
  *   FSF_OPT_POOL_BRUTE (1): fsf_dynamic_point_pool through the P x R brute-force passes instead of the cell-binned path
  *                           (initial value: the environment variable FSF_POOL_BRUTE at load time, else 0).
  *   FSF_OPT_HOST_WAITS (2), read-only: how many times the library has made the calling host thread wait for a stream since it was
- *                           loaded (every count / flag read-back of every entry point) — what bench.py reports as host waits. */
+ *                           loaded (every count / flag read-back of every entry point) — what bench.py reports as host waits.
+ *   FSF_OPT_SIR_FUSED (3): fsf_sir_stack_forward runs a block's input kernel and its first layer as ONE launch
+ *                           (fsf_sir_input_linear_segmax) where that entry point takes the shape — 1: in stacks of at least
+ *                           FSF_SIR_FUSED_MIN_ROWS rows, 2: in every stack (tests, per-shape measurements), 0: never (the two
+ *                           kernels).  Same bits in every setting (initial value: the environment variable FSF_SIR_FUSED at load
+ *                           time, else FSF_SIR_FUSED_DEFAULT). */
 #define FSF_OPT_POOL_BRUTE 1
 #define FSF_OPT_HOST_WAITS 2
+#define FSF_OPT_SIR_FUSED 3
 int fsf_set_option(int32_t option, int64_t value);
 int64_t fsf_get_option(int32_t option);
 
@@ -915,12 +921,32 @@ int fsf_sir_input_gather(const float* points, int64_t points_stride, int32_t p_c
                          const float* g1, const float* b1, int32_t h1, const float* w2, const float* g2, const float* b2, int32_t h2,
                          const float* w3, const float* g3, const float* b3, float eps, int32_t act, int64_t n, float* out,
                          int64_t out_stride, void* stream);
+/* K21 + K22s in ONE launch (csrc/sir_linear.hip): fsf_sir_input_gather followed by the block's first layer,
+ * fsf_linear_f16w_norm_act_segmax(x = K21's output, k = p_cols + feature columns + e_cols, no per-row addend), without the [n, k]
+ * matrix between them reaching memory — K21's product stays in the LDS tile it is formed in and the layer's k chunks are read from
+ * there.  The arguments up to `n` are fsf_sir_input_gather's (mlp_eps / mlp_act: its eps / act), the rest
+ * fsf_linear_f16w_norm_act_segmax's from w_planes on (prepared for k input columns).  Both halves are the two kernels' own code on the
+ * same values in the same order: seg_out and out are BIT-IDENTICAL to the two calls'.
+ * Scope: 128 < k <= 192, 64 < c <= 128, norm 1 (LayerNorm), act 1 | 2 and mlp_act == act (what the SIR stacks of the FSF configs
+ * run: k = 180 | 133 | 136 | 181 | 146 -> 128); FSF_ERR_UNSUPPORTED otherwise, and the caller runs the two kernels. */
+int fsf_sir_input_linear_segmax(const float* points, int64_t points_stride, int32_t p_cols, const float xyz_normalizer[3],
+                                const float* const* feat_parts, const int64_t* feat_strides, const int32_t* feat_cols, int32_t num_parts,
+                                const int64_t* feats_index, int32_t direct_parts_mask, const float* extra, int64_t extra_stride,
+                                int32_t e_cols, float extra_div, const float* f_cluster, int64_t f_cluster_stride, int32_t r_cols,
+                                float rel_div, const float* w1, const float* g1, const float* b1, int32_t h1, const float* w2,
+                                const float* g2, const float* b2, int32_t h2, const float* w3, const float* g3, const float* b3,
+                                float mlp_eps, int32_t mlp_act, int64_t n, const void* w_planes, int32_t c, const float* bias,
+                                int32_t norm, const float* gamma, const float* beta, float eps, int32_t act, const int64_t* seg_ids,
+                                int64_t num_segments, float* seg_out, int64_t seg_out_stride, float* out, int64_t out_stride,
+                                void* stream);
 
 /* K31 (round 6)  a whole SIR stack on rows SORTED by group as one call: SIR.forward (projects/mmdet3d_plugin/models/backbones/sir.py:65-85)
  * and FullySparseBboxHead.forward (models/roi_heads/bbox_heads/fsd_bbox_head.py:96-197) at test time.  Per block: fsf_sir_input_gather (the
  * block's input rows), then per DynamicVFELayer fsf_linear[_f16w]_norm_act_segmax, preceded from the second layer on by the group half of
  * the layer's weight on the previous layer's group maxima (fsf_linear_norm_act / fsf_linear_f16w_norm_act_grouped on [num_groups, c]) —
- * the calls hip_ops.sir_input / sst_ops.sorted_stack_forward issue from Python, with the same arguments, sequenced from C++.
+ * the calls hip_ops.sir_input / sst_ops.sorted_stack_forward issue from Python, with the same arguments, sequenced from C++.  With
+ * FSF_OPT_SIR_FUSED set (1: and n >= FSF_SIR_FUSED_MIN_ROWS; 2: any n) a block's first two calls are tried as one (fsf_sir_input_linear_segmax: the same
+ * bits); where that returns FSF_ERR_UNSUPPORTED the two calls run.
  *   blocks        HOST array [num_blocks]; device pointers inside: the position MLP (w* f32 row-major, g* / b* LayerNorm affine), per layer
  *                 the prepared weights of the point half (`planes_left`, fsf_linear_prepare_weight[_f16]; *_f16 != 0: the f16 format)
  *                 and — layers >= 1 — of the group half (`planes_right`), bias / gamma / beta (or NULL), norm / act codes of
@@ -933,6 +959,9 @@ int fsf_sir_input_gather(const float* points, int64_t points_stride, int32_t p_c
  *   arena         device, 256-byte aligned, >= fsf_sir_stack_arena_bytes(blocks, num_blocks, n, num_groups).
  * n >= 1, num_groups >= 1 (the host path keeps the degenerate cases). */
 #define FSF_SIR_MAX_LAYERS 4
+#define FSF_SIR_FUSED_DEFAULT 1       /* on: shorter than the pair on every call shape, 0.35 ms per frame (profiles/r7_sir_fused_*.txt) */
+#define FSF_SIR_FUSED_MIN_ROWS 1      /* no shape class is routed to the pair: the fused launch is the shorter one from 500 rows up */
+#define FSF_SIR_FUSED_BLOCK_ROWS 128  /* rows a workgroup of the fused kernel takes per iteration (8 waves x one 16-row group) */
 typedef struct {
   const void* planes_left;
   const void* planes_right;
