@@ -11,18 +11,6 @@ typedef _Float16 lna_f16x4 __attribute__((ext_vector_type(4)));
 typedef float lna_f32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned lna_u32x4 __attribute__((ext_vector_type(4)));
 
-#ifdef FSF_LNA_TIMELINE  // profiling build only (tools/profiling/lna_timeline.sh): where a workgroup's wave 0 spends its clocks
-struct LnaTl {
-  unsigned long long last, acc[8];
-  __device__ __forceinline__ void start() { last = __builtin_readcyclecounter(); for (int i = 0; i < 8; ++i) acc[i] = 0; }
-  __device__ __forceinline__ void mark(int i) { const unsigned long long now = __builtin_readcyclecounter(); acc[i] += now - last; last = now; }
-};
-#define LNA_TL_MARK(tl, i) (tl).mark(i)
-#else
-struct LnaTl {};
-#define LNA_TL_MARK(tl, i) ((void)0)
-#endif
-
 constexpr int LNA_KC = 32;        // k per LDS chunk (one MFMA k step)
 constexpr int LNA_NW = 4;         // waves per workgroup (two workgroups per CU: one wave of each per SIMD)
 constexpr int LNA_RG = 2;         // 16-row groups per wave and iteration
@@ -298,7 +286,7 @@ template <int T, bool SEG = false, int NORM_CT = -1, int ACT_CT = -1, int RG = L
 // max-scan; NORM_CT / ACT_CT >= 0: norm and activation fixed at compile time (the K22s variants: their epilogue is already twice
 // the code, and the run-time switches of the plain kernel would double it again)
 __device__ __forceinline__ void lna_epilogue(const LnaArgs& a, lna_f32x4 (&acc)[RG][T], int64_t row0, int ch_base, int rowl,
-                                             int grp, const float* vec, LnaTl& tl, const LnaSegBlockT<RG>* sb = nullptr) {
+                                             int grp, const float* vec, const LnaSegBlockT<RG>* sb = nullptr) {
   const float inv_c = 1.0f / (float)a.norm_w;
   // the arithmetic below runs on pairs (v_pk_*_f32): the same IEEE operations per value as the scalar form, half the instructions
   auto lo = [](const lna_f32x4& v) { return lna_f32x2{v[0], v[1]}; };
@@ -342,7 +330,6 @@ __device__ __forceinline__ void lna_epilogue(const LnaArgs& a, lna_f32x4 (&acc)[
         }
       }
     }
-    LNA_TL_MARK(tl, 2);  // segment context + bias + the per-row addend (its gather is waited for here)
     if ((NORM_CT >= 0 ? NORM_CT : a.norm) == 1) {  // LayerNorm over the c channels (channels >= c are exactly 0: zero weights, no bias)
       lna_f32x2 s2 = lna_pk(0.0f);
 #pragma unroll
@@ -359,7 +346,6 @@ __device__ __forceinline__ void lna_epilogue(const LnaArgs& a, lna_f32x4 (&acc)[
       }
       rstd = rsqrtf(lna_row_sum(q2.x + q2.y) * inv_c + a.eps);
     }
-    LNA_TL_MARK(tl, 3);  // LayerNorm statistics
     if (row < a.n || SEG) {
       float* orow = a.out + row * a.out_stride;
       const lna_f32x2 m2 = lna_pk(mean), r2 = lna_pk(rstd);
@@ -367,22 +353,12 @@ __device__ __forceinline__ void lna_epilogue(const LnaArgs& a, lna_f32x4 (&acc)[
       for (int t = 0; t < T; ++t) {
         const int ch0 = ch_base + 16 * t + g4;
         if (16 * t + 4 * grp < a.slice_w && ch_base + 16 * t + 4 * grp < a.c) {
-#ifdef FSF_ABL_LNA_NO_VEC  // ablation: no LDS reads of gamma / beta in the tile loop (constants: WRONG results)
-          const float4 g = make_float4(1.f, 1.f, 1.f, 1.f), b = make_float4(0.f, 0.f, 0.f, 0.f);
-#else
           const float4 g = *reinterpret_cast<const float4*>(vec + 128 + 16 * t + 4 * grp);  // (1 / 0 without a norm)
           const float4 b = *reinterpret_cast<const float4*>(vec + 256 + 16 * t + 4 * grp);
-#endif
           const lna_f32x2 yl = lna_act2((lo(acc[rg][t]) - m2) * r2 * lna_f32x2{g.x, g.y} + lna_f32x2{b.x, b.y}, ACT_CT >= 0 ? ACT_CT : a.act);
           const lna_f32x2 yh = lna_act2((hi(acc[rg][t]) - m2) * r2 * lna_f32x2{g.z, g.w} + lna_f32x2{b.z, b.w}, ACT_CT >= 0 ? ACT_CT : a.act);
           const float4 y = make_float4(yl.x, yl.y, yh.x, yh.y);
-#if defined(FSF_ABL_LNA_COAL_ST)  // ablation (WRONG places, same bytes): every store instruction writes 1 KB of consecutive addresses
-          if (!SEG || (a.out && row < a.n)) *reinterpret_cast<float4*>(orow - (int64_t)rowl * a.out_stride + t * 256 + (rowl + 16 * grp) * 4) = y;
-#elif !defined(FSF_ABL_LNA_NO_STORE)
           if (!SEG || (a.out && row < a.n)) *reinterpret_cast<float4*>(orow + ch0) = y;
-#else
-          if (y.x == 123.456f) *reinterpret_cast<float4*>(orow + ch0) = y;
-#endif
           if constexpr (SEG) {
             const float4 mx = lna_seg_scan(sc, y);  // (a group past the last row scans copies of row n - 1 and writes nothing)
             if (sc.write) {
@@ -393,7 +369,6 @@ __device__ __forceinline__ void lna_epilogue(const LnaArgs& a, lna_f32x4 (&acc)[
         }
       }
     }
-    LNA_TL_MARK(tl, 4);  // affine + activation + stores (+ the segmented scan and its run stores)
   }
 }
 

@@ -27,10 +27,6 @@
 
 namespace fsf {
 
-#ifdef FSF_LNA_TIMELINE
-__device__ unsigned long long lna_tl[16];
-#endif
-
 // weight [c, k] fp32 -> fragment-ordered bf16 planes (zero padded to T tiles x KP)
 __global__ void __launch_bounds__(256)
     lna_prepare_kernel(const float* __restrict__ w, int k, int c, int T, int nkc, int nslice, int slice_w, uint4* planes) {
@@ -185,22 +181,20 @@ __global__ void __launch_bounds__(256)
 }
 
 
-// NW waves per workgroup.  A weight chunk enters the CU once per WORKGROUP and chunk (LDS-DMA), so three 4-wave workgroups per CU
-// take the same 24 KB in three times per 128 rows each; ONE 12-wave workgroup per CU (same 12 waves, same registers) takes it in
+// LNA_NW = 4 waves per workgroup.  A weight chunk enters the CU once per WORKGROUP and chunk (LDS-DMA), so three 4-wave workgroups per
+// CU take the same 24 KB in three times per 128 rows each; ONE 12-wave workgroup per CU (same 12 waves, same registers) would take it in
 // once per 384 rows.  Measured (round 3, same box): no faster in isolation (510 k x 256 -> 128: 277 vs 279 us; k = 128 .. 180: 5-15 %
 // SLOWER — a barrier over twelve waves per chunk) and 7 % slower in the frame (a 768-thread workgroup shuts the other stream's kernels
-// out of its CU) — so the weight stream is not what this kernel waits for.  Kept behind FSF_K22_WIDE_MIN_ROWS=<rows> (default: never).
-template <int T, int NW, bool SEG = false, int NORM_CT = -1, int ACT_CT = -1, int XM = 0>  // 16-channel tiles (c <= 16 T); SEG: +
+// out of its CU) — so the weight stream is not what this kernel waits for, and the 12-wave form is gone (profiles/r3_k22_ablations.txt).
+template <int T, bool SEG = false, int NORM_CT = -1, int ACT_CT = -1, int XM = 0>  // 16-channel tiles (c <= 16 T); SEG: +
 // segmented max of the output (rows sorted by segment), norm / act fixed at compile time; XM = 1 (XP): x and W arrive as f16 hi | lo
 // planes (K22h); XM = 2 (XF, K22f): fp32 x split IN the kernel into f16 hi | lo of x * s_row (s_row: the running power-of-two unit of the
 // row, below), W as f16 planes — three MFMA passes per product instead of the six of the exact bf16 split (XM = 0)
-__global__ void __launch_bounds__(NW * 64, NW == 4 ? (SEG ? LNA_SEG_WPS : LNA_WPS) : 3) linear_norm_act_kernel(LnaArgs a) {
-  constexpr int LNA_NW = NW;
-  constexpr int LNA_ROWS = NW * LNA_RG * 16;
+__global__ void __launch_bounds__(LNA_NW * 64, SEG ? LNA_SEG_WPS : LNA_WPS) linear_norm_act_kernel(LnaArgs a) {
   constexpr bool XP = XM == 1, XF = XM == 2;
   constexpr int NPL = XM != 0 ? 2 : 3;        // weight planes per tile
   constexpr int CHUNK_U4 = T * NPL * 64;      // uint4 per weight chunk
-  static_assert(!SEG || (NW == 4 && CHUNK_U4 * 16 >= 16 * 128 * 4), "the segmented max parks 16 x 128 floats in a weight buffer");
+  static_assert(!SEG || (LNA_NW == 4 && CHUNK_U4 * 16 >= 16 * 128 * 4), "the segmented max parks 16 x 128 floats in a weight buffer");
   extern __shared__ __attribute__((aligned(16))) char lna_smem[];
   uint4* wbuf = reinterpret_cast<uint4*>(lna_smem);  // [2][CHUNK_U4], then 384 floats of per-channel vectors (, then LnaSegSmem)
   float* vec = reinterpret_cast<float*>(wbuf + 2 * CHUNK_U4);
@@ -214,13 +208,13 @@ __global__ void __launch_bounds__(NW * 64, NW == 4 ? (SEG ? LNA_SEG_WPS : LNA_WP
   // XP launches come as a 1-D grid laid out so that the workgroups that share a row block (one per 128-channel slice) have the same
   // id modulo 8, i.e. land on the same XCD and meet their x rows in its L2: id = xcd + 8 (slice + nslice j), row-block lane 8 j + xcd
   int slice_id = (int)blockIdx.y;
-  int64_t blk_first_ = blockIdx.x, blk_step_ = gridDim.x;
+  int64_t blk_first = blockIdx.x, blk_step = gridDim.x;
   if constexpr (XP) {
     const int nslice = (a.c + a.slice_w - 1) / a.slice_w;
     const int wg = (int)blockIdx.x, q = wg >> 3;
     slice_id = q % nslice;
-    blk_first_ = (int64_t)(q / nslice) * 8 + (wg & 7);
-    blk_step_ = gridDim.x / nslice;
+    blk_first = (int64_t)(q / nslice) * 8 + (wg & 7);
+    blk_step = gridDim.x / nslice;
   }
   const int ch_base = a.slice_w * slice_id;
   const uint4* planes = a.planes + (XM != 0 ? 16 : 0) + (int64_t)slice_id * nkc * CHUNK_U4;  // (f16 planes: behind the 256-byte header)
@@ -229,9 +223,6 @@ __global__ void __launch_bounds__(NW * 64, NW == 4 ? (SEG ? LNA_SEG_WPS : LNA_WP
 
   // weight chunk kc -> LDS buffer by LDS-DMA: fragment order in HBM == fragment order in LDS, 1 KB per wave instruction
   auto stage_w = [&](int kc, int buf) {
-#ifdef FSF_ABL_LNA_NO_W  // ablation: the weight chunks are staged once (chunk 0 into both buffers), never again
-    if (kc > 1) return;
-#endif
     const float* src = reinterpret_cast<const float*>(planes + (int64_t)kc * CHUNK_U4);
     float* dst = reinterpret_cast<float*>(wbuf + buf * CHUNK_U4);
     for (int u = wave * 64; u < CHUNK_U4; u += LNA_NW * 64)
@@ -247,9 +238,6 @@ __global__ void __launch_bounds__(NW * 64, NW == 4 ? (SEG ? LNA_SEG_WPS : LNA_WP
     for (int rg = 0; rg < LNA_RG; ++rg) {
       int64_t r = blk * LNA_ROWS + (int64_t)wave * (LNA_RG * 16) + 16 * rg + rowl;
       if (r >= a.n) r = a.n - 1;  // rows past n repeat the last one (finite, never stored)
-#ifdef FSF_ABL_LNA_X_HOT  // ablation: every x load hits one of 4096 cache-resident rows
-      r &= 4095;
-#endif
       if constexpr (XP) xrow[rg] = a.x + r * (int64_t)a.k;  // (plane rows: k / 8 blocks x 2 planes x 16 B = 4 k bytes, like fp32 rows)
       else xrow[rg] = a.x + r * a.x_stride + (int64_t)slice_id * a.x_slice_off;
     }
@@ -270,23 +258,12 @@ __global__ void __launch_bounds__(NW * 64, NW == 4 ? (SEG ? LNA_SEG_WPS : LNA_WP
         continue;
       }
       const int kq = kc * LNA_KC + 8 * grp;  // this lane's 8 k values
-#ifdef FSF_ABL_LNA_COAL_X  // ablation (WRONG values, same bytes): every load instruction reads 1 KB of consecutive addresses, lane by lane
-      const float* cb = xrow[rg] - (int64_t)rowl * a.x_stride + (lane & 63) * 4;
-      const float4 p = *reinterpret_cast<const float4*>(cb + ((2 * kc) & 7) * 256);
-      const float4 q = *reinterpret_cast<const float4*>(cb + ((2 * kc + 1) & 7) * 256);
-#else
       const float4 p = *reinterpret_cast<const float4*>(xrow[rg] + min(kq, last_quad));
       const float4 q = *reinterpret_cast<const float4*>(xrow[rg] + min(kq + 4, last_quad));
-#endif
       v[rg][0] = p.x; v[rg][1] = p.y; v[rg][2] = p.z; v[rg][3] = p.w;
       v[rg][4] = q.x; v[rg][5] = q.y; v[rg][6] = q.z; v[rg][7] = q.w;
     }
   };
-  // row blocks of this workgroup: strided over the grid, or (SEG) one contiguous range, so that a segment's rows meet in one
-  // workgroup wherever they can
-  const int64_t blk_first = blk_first_;
-#define LNA_BLK_END nblk
-#define LNA_BLK_STEP blk_step_
   lna_stage_vectors(a, ch_base, vec);
   // (XF) the weight scale s_w, and the cap of a row's FIRST scale: with a per-row addend in the accumulators — it enters them multiplied
   // by s * s_w — s * s_w stays <= 2^40 (an addend below 2^87 cannot overflow; a row whose values all lie below 2^-27 / s_w loses bits
@@ -301,10 +278,6 @@ __global__ void __launch_bounds__(NW * 64, NW == 4 ? (SEG ? LNA_SEG_WPS : LNA_WP
       xs_cap_inv = __uint_as_float((unsigned)(127 - e) << 23);
     }
   }
-  LnaTl tl;
-#ifdef FSF_LNA_TIMELINE
-  tl.start();
-#endif
   // The per-row addend (`cat([point, group[inv]]) W^T` = point W_left^T + (group W_right^T)[inv]) enters through the ACCUMULATORS: they
   // start a row block as the gathered addend rows instead of zeros, the MFMAs accumulate on top.  In the epilogue (round 4) the gather
   // was four exposed round trips per block — index, then 4 + 4 tiles per row group, twice — 20 % of the grouped K22s kernel
@@ -324,13 +297,13 @@ __global__ void __launch_bounds__(NW * 64, NW == 4 ? (SEG ? LNA_SEG_WPS : LNA_WP
   a_epi.row_add = nullptr;
   float xc[LNA_RG][8];
   int buf = 0;
-  if (blk_first < LNA_BLK_END) {
+  if (blk_first < nblk) {
     fetch_addend_index(blk_first);
     set_rows(blk_first);
     load_x(0, xc);
     stage_w(0, 0);
   }
-  for (int64_t blk = blk_first; blk < LNA_BLK_END; blk += LNA_BLK_STEP) {
+  for (int64_t blk = blk_first; blk < nblk; blk += blk_step) {
     const int64_t row0 = blk * LNA_ROWS + (int64_t)wave * (LNA_RG * 16);
     LnaSegBlock sb;
     if constexpr (SEG) {  // the rows' segment ids (and those of the rows just above / below the wave's 32) arrive under the chunk loop
@@ -370,16 +343,6 @@ __global__ void __launch_bounds__(NW * 64, NW == 4 ? (SEG ? LNA_SEG_WPS : LNA_WP
         xinv[rg] = a.x_inv_scale[r < a.n ? r : a.n - 1];
       }
     }
-#ifdef FSF_ABL_LNA_NO_XBLK  // ablation: every row block starts with an exposed load (the kernel before the cross-block pipeline)
-    if (blk != blk_first) {
-      set_rows(blk);
-      load_x(0, xc);
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      __builtin_amdgcn_s_barrier();
-      asm volatile("" ::: "memory");
-      stage_w(0, buf);
-    }
-#endif
     for (int kc = 0; kc < nkc; ++kc, buf ^= 1) {
       // split the chunk that arrived while the previous one was multiplied; its registers then take the next prefetch
       lna_u32x4 xh[LNA_RG], xm[LNA_RG], xl[LNA_RG];
@@ -408,23 +371,19 @@ __global__ void __launch_bounds__(NW * 64, NW == 4 ? (SEG ? LNA_SEG_WPS : LNA_WP
       }
       // this chunk's weights (DMA issued one iteration ago, before that iteration's MFMAs) have landed; the raw barrier
       // carries no fence, so nothing else is drained with them
-      LNA_TL_MARK(tl, 0);  // chunk work: the previous chunk's MFMAs (issue), this chunk's split
       asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
       __builtin_amdgcn_s_barrier();  // + every wave is done reading buffer buf^1
       asm volatile("" ::: "memory");
-      LNA_TL_MARK(tl, 1);  // waiting: this chunk's x and weights, the LDS reads, the barrier
       if (kc + 1 < nkc) {
         stage_w(kc + 1, buf ^ 1);
         load_x(kc + 1, xc);
       }
-#ifndef FSF_ABL_LNA_NO_XBLK
-      else if (blk + LNA_BLK_STEP < LNA_BLK_END) {  // first chunk of the next row block
+      else if (blk + blk_step < nblk) {  // first chunk of the next row block
         stage_w(0, buf ^ 1);
-        set_rows(blk + LNA_BLK_STEP);
+        set_rows(blk + blk_step);
         load_x(0, xc);
-        fetch_addend_index(blk + LNA_BLK_STEP);
+        fetch_addend_index(blk + blk_step);
       }
-#endif
       const uint4* wc = wbuf + buf * CHUNK_U4;
       // Two channel tiles x LNA_RG row groups = 4 independent accumulators per product term: consecutive MFMAs never hit
       // the same accumulator
@@ -450,12 +409,8 @@ __global__ void __launch_bounds__(NW * 64, NW == 4 ? (SEG ? LNA_SEG_WPS : LNA_WP
 #pragma unroll
             for (int rg = 0; rg < LNA_RG; ++rg) {
               const lna_u32x4 xb = TERM_X[term] == 0 ? xh[rg] : TERM_X[term] == 1 ? xm[rg] : xl[rg];
-#ifndef FSF_ABL_LNA_NO_MFMA
               acc[rg][t + tt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wfr[tt][TERM_W[term]], __builtin_bit_cast(lna_bf16x8, xb),
                                                                         acc[rg][t + tt], 0, 0, 0);
-#else  // ablation: one VALU op per product term keeps the operand loads alive without the matrix pipe
-              acc[rg][t + tt][term & 3] += __uint_as_float(xb[term & 3] ^ __builtin_bit_cast(lna_u32x4, wfr[tt][TERM_W[term]])[term & 3]);
-#endif
             }
       }
       }
@@ -475,23 +430,12 @@ __global__ void __launch_bounds__(NW * 64, NW == 4 ? (SEG ? LNA_SEG_WPS : LNA_WP
       __builtin_amdgcn_s_waitcnt(0xc07f);  // lgkmcnt(0): this wave's LDS reads of the last chunk have returned ...
       __builtin_amdgcn_s_barrier();        // ... and so have every other wave's: the slots may overlay that buffer
       if (lane < 4) segsm->slot_sid[4 * wave + lane] = -1;
-      LNA_TL_MARK(tl, 0);  // (the last chunk's MFMAs + the barrier that frees the slot buffer)
-      lna_epilogue<T, true, NORM_CT, ACT_CT>(a_epi, acc, row0, ch_base, rowl, grp, vec, tl, &sb);
+      lna_epilogue<T, true, NORM_CT, ACT_CT>(a_epi, acc, row0, ch_base, rowl, grp, vec, &sb);
       lna_seg_merge(a, slots, segsm);
-      LNA_TL_MARK(tl, 5);  // the block's slot merge (a barrier + 128 threads)
     } else {
-      LNA_TL_MARK(tl, 0);
-      lna_epilogue<T, false>(a_epi, acc, row0, ch_base, rowl, grp, vec, tl);
+      lna_epilogue<T, false>(a_epi, acc, row0, ch_base, rowl, grp, vec);
     }
   }
-#undef LNA_BLK_END
-#undef LNA_BLK_STEP
-#ifdef FSF_LNA_TIMELINE
-  if (threadIdx.x == 0) {
-    for (int i = 0; i < 8; ++i) atomicAdd(&lna_tl[i], tl.acc[i]);
-    atomicAdd(&lna_tl[8], 1ull);
-  }
-#endif
 }
 
 }  // namespace fsf
@@ -546,8 +490,7 @@ extern "C" int fsf_linear_prepare_weight_sliced(const float* weight, int32_t k, 
 static int lna_launch(const LnaArgs& a_in, int nslice, hipStream_t stream, bool xp = false, bool xf = false) {
   LnaArgs a = a_in;
   const int T = lna_tiles(a.slice_w < a.c ? a.slice_w : a.c);
-  const int rows = LNA_NW * LNA_RG * 16;
-  const int64_t nblk = (a.n + rows - 1) / rows;
+  const int64_t nblk = (a.n + LNA_ROWS - 1) / LNA_ROWS;
   int64_t gx = (256 * (a.seg_out ? LNA_SEG_WPS : LNA_WPS) + nslice - 1) / nslice;
   if (gx > nblk) gx = nblk;
   if (xp) {  // K22h: 1-D grid, `gx` row-block lanes (a multiple of 8: one XCD per lane) x nslice workgroups each
@@ -555,44 +498,44 @@ static int lna_launch(const LnaArgs& a_in, int nslice, hipStream_t stream, bool 
     gx = (gx + 7) / 8 * 8;
     constexpr size_t smem = (size_t)2 * 8 * 2 * 64 * 16 + 384 * 4;
     static std::atomic<uint64_t> attr_done{0};
-    FSF_HIP_TRY(fsf_set_max_dynamic_lds((const void*)linear_norm_act_kernel<8, 4, false, -1, -1, true>, (int)smem, attr_done));
-    hipLaunchKernelGGL((linear_norm_act_kernel<8, 4, false, -1, -1, true>), dim3((unsigned)(gx * nslice)), dim3(256), smem, stream, a);
+    FSF_HIP_TRY(fsf_set_max_dynamic_lds((const void*)linear_norm_act_kernel<8, false, -1, -1, true>, (int)smem, attr_done));
+    hipLaunchKernelGGL((linear_norm_act_kernel<8, false, -1, -1, true>), dim3((unsigned)(gx * nslice)), dim3(256), smem, stream, a);
     FSF_LAUNCH_CHECK();
     return FSF_OK;
   }
   const dim3 grid((unsigned)gx, (unsigned)nslice);
-#define FSF_LNA_X(T_, NW_, SEG_, NORM_, ACT_, XM_)                                                                                   \
+#define FSF_LNA_X(T_, SEG_, NORM_, ACT_, XM_)                                                                                       \
   do {                                                                                                                              \
-    constexpr size_t smem = (size_t)2 * T_ * (XM_ ? 2 : 3) * 64 * 16 + 384 * 4 + (SEG_ ? sizeof(LnaSegSmem) : 0);                    \
+    constexpr size_t smem = (size_t)2 * T_ * (XM_ ? 2 : 3) * 64 * 16 + 384 * 4 + (SEG_ ? sizeof(LnaSegSmem) : 0);                   \
     static std::atomic<uint64_t> attr_done{0};                                                                                      \
-    FSF_HIP_TRY(fsf_set_max_dynamic_lds((const void*)linear_norm_act_kernel<T_, NW_, SEG_, NORM_, ACT_, XM_>, (int)smem, attr_done)); \
-    hipLaunchKernelGGL((linear_norm_act_kernel<T_, NW_, SEG_, NORM_, ACT_, XM_>), grid, dim3(NW_ * 64), smem, stream, a);           \
+    FSF_HIP_TRY(fsf_set_max_dynamic_lds((const void*)linear_norm_act_kernel<T_, SEG_, NORM_, ACT_, XM_>, (int)smem, attr_done));    \
+    hipLaunchKernelGGL((linear_norm_act_kernel<T_, SEG_, NORM_, ACT_, XM_>), grid, dim3(LNA_NW * 64), smem, stream, a);             \
   } while (0)
-#define FSF_LNA(T_, NW_, SEG_, NORM_, ACT_) FSF_LNA_X(T_, NW_, SEG_, NORM_, ACT_, 0)
+#define FSF_LNA(T_, SEG_, NORM_, ACT_) FSF_LNA_X(T_, SEG_, NORM_, ACT_, 0)
   if (xf) {  // K22f: the 64- and 128-channel-tile forms (what the SIR / VFE / segmentation-head layers are)
     if (a.seg_out) {
       if (a.norm != 1 || (a.act != 1 && a.act != 2)) return FSF_ERR_UNSUPPORTED;
-      if (T == 4 && a.act == 2) FSF_LNA_X(4, 4, true, 1, 2, 2);
-      else if (T == 4) FSF_LNA_X(4, 4, true, 1, 1, 2);
-      else if (T == 8 && a.act == 2) FSF_LNA_X(8, 4, true, 1, 2, 2);
-      else if (T == 8) FSF_LNA_X(8, 4, true, 1, 1, 2);
+      if (T == 4 && a.act == 2) FSF_LNA_X(4, true, 1, 2, 2);
+      else if (T == 4) FSF_LNA_X(4, true, 1, 1, 2);
+      else if (T == 8 && a.act == 2) FSF_LNA_X(8, true, 1, 2, 2);
+      else if (T == 8) FSF_LNA_X(8, true, 1, 1, 2);
       else return FSF_ERR_UNSUPPORTED;
-    } else if (T == 4) FSF_LNA_X(4, 4, false, -1, -1, 2);
-    else if (T == 8) FSF_LNA_X(8, 4, false, -1, -1, 2);
+    } else if (T == 4) FSF_LNA_X(4, false, -1, -1, 2);
+    else if (T == 8) FSF_LNA_X(8, false, -1, -1, 2);
     else return FSF_ERR_UNSUPPORTED;
     FSF_LAUNCH_CHECK();
     return FSF_OK;
   }
   if (a.seg_out) {  // K22s: LayerNorm + GELU / ReLU (the SIR layers), 36 .. 128 channels
     if (a.norm != 1 || (a.act != 1 && a.act != 2)) return FSF_ERR_UNSUPPORTED;
-    if (T == 4 && a.act == 2) FSF_LNA(4, 4, true, 1, 2);
-    else if (T == 4) FSF_LNA(4, 4, true, 1, 1);
-    else if (T == 8 && a.act == 2) FSF_LNA(8, 4, true, 1, 2);
-    else if (T == 8) FSF_LNA(8, 4, true, 1, 1);
+    if (T == 4 && a.act == 2) FSF_LNA(4, true, 1, 2);
+    else if (T == 4) FSF_LNA(4, true, 1, 1);
+    else if (T == 8 && a.act == 2) FSF_LNA(8, true, 1, 2);
+    else if (T == 8) FSF_LNA(8, true, 1, 1);
     else return FSF_ERR_UNSUPPORTED;
-  } else if (T == 2) FSF_LNA(2, 4, false, -1, -1);
-  else if (T == 4) FSF_LNA(4, 4, false, -1, -1);
-  else FSF_LNA(8, 4, false, -1, -1);
+  } else if (T == 2) FSF_LNA(2, false, -1, -1);
+  else if (T == 4) FSF_LNA(4, false, -1, -1);
+  else FSF_LNA(8, false, -1, -1);
 #undef FSF_LNA
 #undef FSF_LNA_X
   FSF_LAUNCH_CHECK();
@@ -785,15 +728,3 @@ extern "C" int fsf_linear_planes_norm_act(const void* x_planes, const float* x_i
             (int)c, nullptr, nullptr, 0, (int)slice_c, (int)slice_c, 0, nullptr, nullptr, 0, x_inv_scales};
   return lna_launch(a, nslice, stream, true);
 }
-
-#ifdef FSF_LNA_TIMELINE
-// profiling build only: clocks wave 0 of every workgroup spent per phase since the last reset ([8] = workgroups counted)
-extern "C" int fsf_debug_lna_timeline(unsigned long long* host16, int reset) {
-  if (host16 && hipMemcpyFromSymbol(host16, HIP_SYMBOL(fsf::lna_tl), 16 * sizeof(unsigned long long)) != hipSuccess) return FSF_ERR_HIP;
-  if (reset) {
-    unsigned long long z[16] = {};
-    if (hipMemcpyToSymbol(HIP_SYMBOL(fsf::lna_tl), z, sizeof(z)) != hipSuccess) return FSF_ERR_HIP;
-  }
-  return FSF_OK;
-}
-#endif

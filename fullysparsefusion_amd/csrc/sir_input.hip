@@ -23,11 +23,7 @@ struct SiStoreDriver {
   __device__ __forceinline__ int64_t next() { gi += gstep; return gi < groups ? gi : -1; }
   __device__ __forceinline__ void begin(int64_t row0) { orow = out + row0 * out_stride + lane; }
   __device__ __forceinline__ void put(int, int t, const float*, float v) {
-#ifdef SI_ABL_NO_STORE  // ablation: no output stores
-    if (v == 123.456f) orow[64 * t] = 0.0f;
-#else
     if (lane + 64 * t < c) orow[64 * t] = v;
-#endif
   }
   __device__ __forceinline__ void next_row() { orow += out_stride; }
   __device__ __forceinline__ void end_group(const float*) {}

@@ -47,7 +47,6 @@ struct SlDriver {
   int64_t blk, blk_step, nblk, groups;
   int buf;
   float w_scale, w_inv;
-  LnaTl tl;
 
   __device__ __forceinline__ int64_t group_of(int64_t b) const {
     const int64_t g = b * SL_NW + wave;
@@ -108,7 +107,7 @@ struct SlDriver {
     __builtin_amdgcn_s_waitcnt(0xc07f);  // lgkmcnt(0): this wave's LDS reads of the last chunk have returned ...
     __builtin_amdgcn_s_barrier();        // ... and so have every other wave's: the slots may overlay that buffer
     if (lane < 2) segsm->slot_sid[2 * wave + lane] = -1;
-    lna_epilogue<SL_T, true, 1, ACT_L, 1>(a, acc, row0, 0, rowl, grp, vec, tl, &sb);
+    lna_epilogue<SL_T, true, 1, ACT_L, 1>(a, acc, row0, 0, rowl, grp, vec, &sb);
     lna_seg_merge(a, slots, segsm);
     blk += blk_step;
   }
@@ -126,7 +125,7 @@ __global__ void __launch_bounds__(SL_NW * 64, 1) sir_linear_kernel(SirInputArgs 
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   SlDriver<NT3, ACT> d{a, wbuf, vec, segsm, a.planes + 16, lane, wave, lane & 15, lane >> 4, (a.k + LNA_KC - 1) / LNA_KC, a.k,
                        (int64_t)blockIdx.x, (int64_t)gridDim.x, (a.n + SL_ROWS - 1) / SL_ROWS, (a.n + 15) / 16, 0,
-                       reinterpret_cast<const float*>(a.planes)[1], reinterpret_cast<const float*>(a.planes)[0], LnaTl{}};
+                       reinterpret_cast<const float*>(a.planes)[1], reinterpret_cast<const float*>(a.planes)[0]};
   lna_stage_vectors(a, 0, vec);
   d.stage_w(0, 0);
   si_run<NT3, ACT, SL_NW>(si, si_smem, d);

@@ -27,7 +27,7 @@ extern std::atomic<int64_t> g_opt_sir_fused;  // status.hip (fsf_set_option(FSF_
 
 static inline int64_t sst_pad4(int64_t c) { return (c + 3) / 4 * 4; }
 
-static int sst_widths(const FsfSirBlock* blocks, int32_t num_blocks, int32_t in_cols0, int32_t e_cols, int64_t* x_cols_max, int64_t* c_max) {
+static int sst_widths(const FsfSirBlock* blocks, int32_t num_blocks, int64_t* x_cols_max, int64_t* c_max) {
   // block b's K21 output is [n, in_cols_b] with in_cols_0 given and in_cols_b = p_cols + (last width of block b - 1) + e_cols afterwards:
   // the caller states in_cols per block (`in_cols`), checked against the position MLP's width by fsf_sir_input_gather itself
   int64_t xm = 0, cm = 0;
@@ -40,7 +40,6 @@ static int sst_widths(const FsfSirBlock* blocks, int32_t num_blocks, int32_t in_
       cm = std::max<int64_t>(cm, k.layer[i].c);
     }
   }
-  (void)in_cols0; (void)e_cols;
   *x_cols_max = xm;
   *c_max = cm;
   return FSF_OK;
@@ -48,7 +47,7 @@ static int sst_widths(const FsfSirBlock* blocks, int32_t num_blocks, int32_t in_
 
 extern "C" int64_t fsf_sir_stack_arena_bytes(const FsfSirBlock* blocks, int32_t num_blocks, int64_t n, int64_t num_groups) {
   int64_t xm = 0, cm = 0;
-  if (!blocks || num_blocks < 1 || n < 0 || num_groups < 0 || sst_widths(blocks, num_blocks, 0, 0, &xm, &cm) != FSF_OK) return 0;
+  if (!blocks || num_blocks < 1 || n < 0 || num_groups < 0 || sst_widths(blocks, num_blocks, &xm, &cm) != FSF_OK) return 0;
   const int64_t nn = n > 0 ? n : 1, gg = num_groups > 0 ? num_groups : 1;
   return fsf_align_up(nn * xm * 4, 256) + 2 * fsf_align_up(nn * cm * 4, 256) + 2 * fsf_align_up(gg * cm * 4, 256) + 256;
 }
@@ -63,7 +62,7 @@ extern "C" int fsf_sir_stack_forward(const FsfSirBlock* blocks, int32_t num_bloc
   if (!blocks || num_blocks < 1 || n < 1 || num_groups < 1 || !points || !f_cluster || !seg_ids || !groups || !arena) return FSF_ERR_INVALID_ARG;
   if (((uintptr_t)arena & 255) || arena_bytes < fsf_sir_stack_arena_bytes(blocks, num_blocks, n, num_groups)) return FSF_ERR_WORKSPACE;
   int64_t xm = 0, cm = 0;
-  int rc = sst_widths(blocks, num_blocks, 0, 0, &xm, &cm);
+  int rc = sst_widths(blocks, num_blocks, &xm, &cm);
   if (rc != FSF_OK) return rc;
   char* base = (char*)arena;
   float* xbuf = (float*)base;

@@ -248,14 +248,6 @@ __device__ __forceinline__ void fold_tile(const SpconvArgs& a, const float* Cs, 
   }
 }
 
-#ifdef FSF_ABL_TIMING
-__device__ long long fsf_dbg[4096 * 8];
-#define FSF_BID ((item[0] * a.cout_blocks + item[1]) * a.ksplit + item[2])
-#define FSF_STAMP(i) do { if (threadIdx.x == 0 && FSF_BID < 4096) fsf_dbg[FSF_BID * 8 + (i)] = wall_clock64(); } while (0)
-#else
-#define FSF_STAMP(i) do { } while (0)
-#endif
-
 // ------------------------------------------------------------------------------------------------------
 // Fast path: cin % 64 == 0.  LDS-DMA double-buffered A tile, register double-buffered B, one barrier per stage.
 // NW waves per workgroup: 4 (each wave owns TN/4 columns) or 8 (TN/8 columns: twice the waves per SIMD to hide the
@@ -298,10 +290,8 @@ __global__ void __launch_bounds__(NW * 64, (TM == 64 ? 2 : 1) * NW / 4) spconv_f
   const int n0 = item[1] * TN;
   const int zsplit = item[2];
 
-  FSF_STAMP(0);
   // the A buffers double as the staging area of the neighbour-table block
   build_row_lists<TM, NT>(a, o0, zsplit, reinterpret_cast<int32_t*>(As), rl_in, rl_loc, rl_cnt, act_k, act_n);
-  FSF_STAMP(1);
   const int nstages = act_n[0] * nchunks;
 
   f32x4 bcur[NCT][SC_NSTEPS], bnext[NCT][SC_NSTEPS];
@@ -330,11 +320,7 @@ __global__ void __launch_bounds__(NW * 64, (TM == 64 ? 2 : 1) * NW / 4) spconv_f
         const int j = 4 * g + (lane >> 4);
         const int chunk = (lane & 15) ^ (j & 15);  // logical 16-B chunk that must land at physical slot lane&15 of row j
         const float* src = a.feat + goff[it] + cin0 + 4 * chunk;
-#ifndef FSF_ABL_NO_GATHER
         __builtin_amdgcn_global_load_lds(src, abuf + 4 * g * SC_AROW, 16, 0, 0);
-#else
-        asm volatile("" ::"v"(src));
-#endif
       }
     }
   };
@@ -364,13 +350,11 @@ __global__ void __launch_bounds__(NW * 64, (TM == 64 ? 2 : 1) * NW / 4) spconv_f
     issue_gather(cnt, 0, 0);
     load_b(k, 0, bcur);
   }
-  FSF_STAMP(2);
   // C (incl. the dump row) is zeroed while the first stage is in flight.  The A buffers are NOT cleared: rows past an
   // offset's live count hold stale data, but an MFMA output row depends on its own A row only and those rows land in
   // the dump row, which is never read back.
   for (int t = tid; t < SM::CS_FLOATS / 4; t += NT) reinterpret_cast<float4*>(Cs)[t] = make_float4(0.f, 0.f, 0.f, 0.f);
   __syncthreads();  // (the compiler drains the DMA before the barrier) A[0] complete and visible
-  FSF_STAMP(3);
 
   // Accumulators of ALL row blocks of the current offset stay in registers across its cin chunks: the LDS C tile is
   // read once and written once per (offset, row block) instead of once per 64-wide chunk (the C read-modify-write
@@ -392,23 +376,12 @@ __global__ void __launch_bounds__(NW * 64, (TM == 64 ? 2 : 1) * NW / 4) spconv_f
         load_goff(nk, ncnt);
       }
       issue_gather(ncnt, ncin0, cur ^ 1);  // lands in the other A buffer while the matrix cores work on stage s
-#ifndef FSF_ABL_NO_BLOAD
       load_b(nk, ncin0, bnext);
-#else
-#pragma unroll
-      for (int ct = 0; ct < NCT; ++ct)
-#pragma unroll
-        for (int st = 0; st < SC_NSTEPS; ++st) bnext[ct][st] = bcur[ct][st];
-#endif
     }
     {
       const int nrb = (cnt + 15) >> 4;
       const float* abuf = As + cur * ABUF;
-#ifdef FSF_ABL_NO_CRMW
-      if (s == 0) {
-#else
       if (chunk_c == 0) {
-#endif
 #pragma unroll
         for (int rb = 0; rb < MAXRB; ++rb) {
           if (rb < nrb) {
@@ -440,31 +413,19 @@ __global__ void __launch_bounds__(NW * 64, (TM == 64 ? 2 : 1) * NW / 4) spconv_f
           const float* arow = abuf + arow_idx * SC_AROW;
 #pragma unroll
           for (int st = 0; st < SC_NSTEPS; ++st)  // logical chunk 4*st + kgrp lives at physical (chunk ^ (row & 15))
-#ifndef FSF_ABL_NO_AREAD
             af[st] = *reinterpret_cast<const f32x4*>(arow + 4 * ((4 * st + kgrp) ^ (arow_idx & 15)));
-#else
-            af[st] = f32x4{(float)arow_idx, 1.f, 2.f, (float)st};
-#endif
 #pragma unroll
           for (int st = 0; st < SC_NSTEPS; ++st) {
 #pragma unroll
             for (int t = 0; t < 4; ++t) {
 #pragma unroll
               for (int ct = 0; ct < NCT; ++ct)
-#ifndef FSF_ABL_NO_MFMA
                 acc[rb][ct] = __builtin_amdgcn_mfma_f32_16x16x4f32(af[st][t], bcur[ct][st][t], acc[rb][ct], 0, 0, 0);
-#else
-                acc[rb][ct][t] += af[st][t] * bcur[ct][st][t];
-#endif
             }
           }
         }
       }
-#ifdef FSF_ABL_NO_CRMW
-      if (s == nstages - 1) {
-#else
       if (chunk_c == nchunks - 1) {
-#endif
 #pragma unroll
         for (int rb = 0; rb < MAXRB; ++rb) {
           if (rb < nrb) {
@@ -496,11 +457,8 @@ __global__ void __launch_bounds__(NW * 64, (TM == 64 ? 2 : 1) * NW / 4) spconv_f
 #pragma unroll
         for (int st = 0; st < SC_NSTEPS; ++st) bcur[ct][st] = bnext[ct][st];
     }
-#ifndef FSF_ABL_NO_BARRIER
     __syncthreads();  // A[cur^1] landed + visible, everyone is done reading A[cur]
-#endif
   }
-  FSF_STAMP(4);
   write_tile<TN, TM, true, NT>(a, Cs, o0, n0, zsplit);
   if (a.ksplit > 1) {
     // publish the partial tile (write-through stores), then take an arrival ticket: every wave drains its stores,
@@ -517,15 +475,6 @@ __global__ void __launch_bounds__(NW * 64, (TM == 64 ? 2 : 1) * NW / 4) spconv_f
     __syncthreads();
     if (item[3] == a.ksplit - 1) fold_tile<TN, TM, NT>(a, Cs, o0, n0, zsplit);
   }
-  FSF_STAMP(5);
-#ifdef FSF_ABL_TIMING
-  if (threadIdx.x == 0 && FSF_BID < 4096) {
-    fsf_dbg[FSF_BID * 8 + 6] = nstages;
-    unsigned hwid;  // HW_ID: cu_id [11:8], sh [12], se [15:13]; XCC_ID is a separate register
-    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hwid));
-    fsf_dbg[FSF_BID * 8 + 7] = (long long)hwid | ((long long)(xcc & 0xf) << 32);
-  }
-#endif
   }  // work-item loop
 }
 
@@ -708,12 +657,6 @@ static int64_t spconv_queue_bytes(int64_t tiles, int cout_blocks, int ksplit) {
 }  // namespace fsf
 
 using namespace fsf;
-
-#ifdef FSF_ABL_TIMING
-extern "C" int fsf_debug_read(long long* host, int n) {
-  return (int)hipMemcpyFromSymbol(host, HIP_SYMBOL(fsf::fsf_dbg), sizeof(long long) * n, 0, hipMemcpyDeviceToHost);
-}
-#endif
 
 extern "C" int fsf_spconv_transpose_weight(const float* weight, int32_t kvol, int32_t cin, int32_t cout, float* weight_t,
                                            void* stream_) {

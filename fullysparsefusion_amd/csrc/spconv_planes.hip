@@ -412,11 +412,7 @@ __global__ void __launch_bounds__(256, RG == 8 ? 1 : SP_RG4_WPS) spconv_fwd_plan
   const int nsrc = a.c[1] > 0 ? 2 : 1;
   const int nkc0 = FIX ? NKC : a.c[0] / 32, nkc1 = FIX ? (nsrc == 2 ? NKC : 0) : a.c[1] / 32;
   const int nchunks = nkc0 + nkc1;  // 32-cin chunks of the concatenated input (the weight fragments are laid out over them)
-#ifdef SP_ABL_NO_LOOP  // ablation: prologue + epilogue only
-  const int nsteps = 0;
-#else
   const int nsteps = nk * nsrc;
-#endif
   const float w_inv = a.w_hdr[0];
   const uint32_t rowbytes0 = (uint32_t)a.c[0] * 4u, rowbytes1 = (uint32_t)a.c[1] * 4u;
 
@@ -446,9 +442,6 @@ __global__ void __launch_bounds__(256, RG == 8 ? 1 : SP_RG4_WPS) spconv_fwd_plan
     float sc[CPW];
   };
   XStage xs_a;
-#ifdef SP_DEEP
-  XStage xs_b;  // second staging set: the gather runs THREE steps ahead of its use (an L2 miss outlasts one step)
-#endif
   auto load_x = [&](const SpStep& st, XStage& xs) {
     const char* xb = st.src ? a.x[1] : a.x[0];  // (a run-time index would put the whole argument block in scratch)
     const float* sb = st.src ? a.sx[1] : a.sx[0];
@@ -467,11 +460,7 @@ __global__ void __launch_bounds__(256, RG == 8 ? 1 : SP_RG4_WPS) spconv_fwd_plan
       }
       int i = nbr_s[(16 * cc + j) * kvol + st.k];
       i = i >= 0 ? i : (int)a.m_in;
-#ifdef SP_ABL_NO_X
-      const char* p = xb + (uint32_t)(i & 15) * rb + (uint32_t)(sp_kgroup(q) * 32);
-#else
       const char* p = xb + (uint32_t)i * rb + (uint32_t)(sp_kgroup(q) * 32);  // (planes < 4 GiB: checked by the host; k group: see sp_kgroup)
-#endif
 #pragma unroll
       for (int kc = 0; kc < SP_NKC; ++kc) {
         if (FIX ? kc < NKC : true) {  // (run-time widths: chunks past the row's end are never stored; the address stays inside the planes of row i + 1 or the zero row's successor — see the host check)
@@ -483,9 +472,6 @@ __global__ void __launch_bounds__(256, RG == 8 ? 1 : SP_RG4_WPS) spconv_fwd_plan
     }
   };
   auto store_x = [&](const SpStep& st, int slot, const XStage& xs) {  // registers -> LDS in B-fragment order (lane-linear: conflict-free)
-#ifdef SP_ABL_NO_LDS_WRITE
-    return;
-#endif
     const int nkc = FIX ? NKC : (st.src ? nkc1 : nkc0);
 #pragma unroll
     for (int u = 0; u < CPW; ++u) {
@@ -505,15 +491,8 @@ __global__ void __launch_bounds__(256, RG == 8 ? 1 : SP_RG4_WPS) spconv_fwd_plan
   };
   // this wave's A fragments of chunk kc of step st (16 * TPW channels x 32 cin, hi | lo)
   auto load_w = [&](const SpStep& st, int kc, uint4 (&wf)[TPW][2]) {
-#ifdef SP_ABL_NO_W
-    if (st.kidx > 0 || st.src > 0 || kc > 0) return;
-#endif
     const int c = (st.src ? nkc0 : 0) + kc;
-#ifdef SP_ABL_W_SAME  // ablation: every step fetches offset 0's fragments (same instructions, the lines stay in the CU's L1)
-    const int wk = 0;
-#else
     const int wk = st.k;
-#endif
     const uint4* p = reinterpret_cast<const uint4*>(a.w) +
                      ((((int64_t)slice * kvol + wk) * nchunks + c) * 4 + wave) * (TPW * 2 * 64) + lane;
 #pragma unroll
@@ -527,9 +506,6 @@ __global__ void __launch_bounds__(256, RG == 8 ? 1 : SP_RG4_WPS) spconv_fwd_plan
   // One cell's fragments of chunk kc: the cell's registers are re-read for chunk kc + 1 as soon as its MFMAs are issued (the
   // other cells' MFMAs cover the LDS latency), so one register set serves the whole step.
   auto read_cell = [&](int slot, int kc, int g, uint4& xh, uint4& xl) {
-#ifdef SP_ABL_NO_LDS_READ
-    return;
-#endif
     const uint4* xs = xring + (((slot * RG + g) * SP_NKC + kc) * 2) * 64 + lane;
     xh = xs[0];
     xl = xs[64];
@@ -537,11 +513,6 @@ __global__ void __launch_bounds__(256, RG == 8 ? 1 : SP_RG4_WPS) spconv_fwd_plan
   // chunk kc of one cell; the first chunk starts the step's products from zero (no clearing pass over D)
   auto mma_cell = [&](int kc, int g, const uint4& xh, const uint4& xl, uint4 (&wk)[TPW][2]) {
     const sp_f16x8 bh = __builtin_bit_cast(sp_f16x8, xh), bl = __builtin_bit_cast(sp_f16x8, xl);
-#ifdef SP_ABL_NO_MFMA
-#pragma unroll
-    for (int t = 0; t < TPW; ++t)
-      D[g][t][0] = (kc == 0 ? 0.0f : D[g][t][0]) + __uint_as_float(xh.x ^ wk[t][0].x ^ xl.y ^ wk[t][1].y);
-#else
     sp_f16x8 wh[TPW], wl[TPW];
 #pragma unroll
     for (int t = 0; t < TPW; ++t) {
@@ -555,25 +526,18 @@ __global__ void __launch_bounds__(256, RG == 8 ? 1 : SP_RG4_WPS) spconv_fwd_plan
     for (int t = 0; t < TPW; ++t) D[g][t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh[t], bl, D[g][t], 0, 0, 0);
 #pragma unroll
     for (int t = 0; t < TPW; ++t) D[g][t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh[t], bh, D[g][t], 0, 0, 0);
-#endif
   };
   // (A second, test-free instruction stream for steps whose cells are all live was tried: with both streams in the loop the
   // kernel spills 37-90 registers at two workgroups per CU and is 50 % slower.)
   // The staging of the following steps rides inside: X(s+1) registers -> LDS and the X(s+2) gather are issued when the last
   // chunk's fragments have been requested, so the LDS queue (in order per wave) never has this step's reads behind the writes
   // and the writes retire under the last chunk's MFMAs (at the top of the step they cost a quarter of the layer).
-#ifndef SP_WD
-#define SP_WD 0
-#endif
-  // -DSP_WD=n (experiment, off): the first n chunks of a step's weights double-buffered and requested TWO steps ahead (set A in even
-  // steps, set B in odd ones, each refilled for step s + 2 behind its own MFMAs), the rest on the one-step rolling refill.  n = 2 fits the
-  // 128-channel variant's registers (254 VGPRs, no spills) and changes nothing (+-1 % per layer): the weight loads' distance is not what
-  // the kernel waits on either.  What did pay is the loop below running two steps per trip with the LDS slot and this parity as
-  // compile-time constants: -2.5 ... 3.5 % on every layer.
-  constexpr int WD = FIX ? (SP_WD < NKC ? SP_WD : NKC) : 0;
-  uint4 wf_b[WD > 0 ? WD : 1][TPW][2];
-  auto compute = [&](auto odd_tag, const SpStep& st, const SpStep& nxt, const SpStep& nxt2, int slot, XStage& xs) {
-    constexpr bool ODD = decltype(odd_tag)::value;
+  // The loop below runs two steps per trip so that the LDS slot is a compile-time constant: -2.5 ... 3.5 % on every layer.  (Also
+  // measured with that shape: the first two chunks of a step's weights double-buffered and requested TWO steps ahead, one register set per
+  // step parity — fits the 128-channel variant's registers and changes nothing, +-1 % per layer: the weight loads' distance is not what
+  // the kernel waits on either.)
+  // (the tag is not read: one instantiation per step parity is what keeps `slot` a constant in each — without it the code differs)
+  auto compute = [&](auto /*odd_tag*/, const SpStep& st, const SpStep& nxt, const SpStep& nxt2, int slot, XStage& xs) {
     const int nkc = FIX ? NKC : (st.src ? nkc1 : nkc0);
     const int nkc_nxt = FIX ? NKC : (nxt.src ? nkc1 : nkc0);
     uint4 xh[RG], xl[RG];
@@ -587,22 +551,19 @@ __global__ void __launch_bounds__(256, RG == 8 ? 1 : SP_RG4_WPS) spconv_fwd_plan
 #pragma unroll
     for (int kc = 0; kc < SP_NKC; ++kc) {
       if (kc < nkc) {
-#ifndef SP_STAGE_EARLY
         if (kc == nkc - 1) {
           store_x(nxt, slot ^ 1, xs);
           load_x(nxt2, xs);
         }
-#endif
 #pragma unroll
         for (int g = 0; g < RG; ++g)
           if ((st.mask >> g) & 1u) {
-            mma_cell(kc, g, xh[g], xl[g], (ODD && kc < WD) ? wf_b[kc < WD ? kc : 0] : wf[kc]);
+            mma_cell(kc, g, xh[g], xl[g], wf[kc]);
             if (kc + 1 < nkc) read_cell(slot, kc + 1, g, xh[g], xl[g]);
           }
       }
       // this chunk's weight registers take the next step's chunk as soon as its MFMAs are issued (a rolling prefetch)
-      if (kc < WD) load_w(nxt2, kc, ODD ? wf_b[kc < WD ? kc : 0] : wf[kc]);  // (two steps ahead, into the set this step has just used)
-      else if (kc < nkc_nxt) load_w(nxt, kc, wf[kc]);
+      if (kc < nkc_nxt) load_w(nxt, kc, wf[kc]);
     }
     // fold the step: this lane's row scale in every live cell
 #pragma unroll
@@ -620,7 +581,7 @@ __global__ void __launch_bounds__(256, RG == 8 ? 1 : SP_RG4_WPS) spconv_fwd_plan
   // ---- main loop.  Step s = (live offset, source): [barrier] [multiply step s from slot s%2 chunk by chunk, W(s+1) rolling in
   // behind; before the last chunk's MFMAs: X(s+1) registers -> LDS slot (s+1)%2, then the X(s+2) gather -> registers].  One barrier
   // per step: it separates the reads of step s-1 from the writes into the same slot, and the writes of X(s) (during step s-1)
-  // from their reads.  (-DSP_STAGE_EARLY: the staging at the top of the step, as it was: 0-3 % slower per layer.)
+  // from their reads.  (The staging at the top of the step, as it was, is 0-3 % slower per layer.)
   SpStep s0 = entry(0, 0);
   SpStep s1 = advance(s0);
   load_x(s0, xs_a);
@@ -629,62 +590,20 @@ __global__ void __launch_bounds__(256, RG == 8 ? 1 : SP_RG4_WPS) spconv_fwd_plan
     if (kc < nkc0) load_w(s0, kc, wf[kc]);
   store_x(s0, 0, xs_a);
   SpStep s2 = advance(s1);
-#if defined(SP_DEEP)
-  // X(s + 1) lives in set B for even s and in set A for odd s; when it has gone to LDS its set takes the gather of X(s + 3)
-  load_x(s1, xs_b);
-  load_x(s2, xs_a);
-  SpStep s3 = advance(s2);
-  int s = 0;
-  for (; s + 1 < nsteps; s += 2) {
-    __syncthreads();
-    compute(std::false_type{}, s0, s1, s3, 0, xs_b);
-    s0 = s1; s1 = s2; s2 = s3; s3 = advance(s3);
-    __syncthreads();
-    compute(std::true_type{}, s0, s1, s3, 1, xs_a);
-    s0 = s1; s1 = s2; s2 = s3; s3 = advance(s3);
-  }
-  if (s < nsteps) {
-    __syncthreads();
-    compute(std::false_type{}, s0, s1, s3, 0, xs_b);
-  }
-#else
   load_x(s1, xs_a);
-  if (WD > 0) {
-#pragma unroll
-    for (int kc = 0; kc < WD; ++kc) load_w(s1, kc, wf_b[kc < WD ? kc : 0]);
-  }
   int s = 0;
-  for (; s + 1 < nsteps; s += 2) {  // (two steps per trip: the weight set of the leading chunks alternates at compile time)
-#ifndef SP_ABL_NO_BARRIER
+  for (; s + 1 < nsteps; s += 2) {  // (two steps per trip: the LDS slot alternates at compile time)
     __syncthreads();
-#endif
-#ifdef SP_STAGE_EARLY
-    store_x(s1, 1, xs_a);
-    load_x(s2, xs_a);
-#endif
     compute(std::false_type{}, s0, s1, s2, 0, xs_a);
     s0 = s1; s1 = s2; s2 = advance(s2);
-#ifndef SP_ABL_NO_BARRIER
     __syncthreads();
-#endif
-#ifdef SP_STAGE_EARLY
-    store_x(s1, 0, xs_a);
-    load_x(s2, xs_a);
-#endif
     compute(std::true_type{}, s0, s1, s2, 1, xs_a);
     s0 = s1; s1 = s2; s2 = advance(s2);
   }
   if (s < nsteps) {
-#ifndef SP_ABL_NO_BARRIER
     __syncthreads();
-#endif
-#ifdef SP_STAGE_EARLY
-    store_x(s1, 1, xs_a);
-    load_x(s2, xs_a);
-#endif
     compute(std::false_type{}, s0, s1, s2, 0, xs_a);
   }
-#endif
 
   sp_epilogue<RG, TPW>(a, acc, vec, rowmax, row0, slice, wave, tid);
 }
@@ -731,13 +650,10 @@ struct SpPipeSmem {
 #ifndef SP_PIPE_WPS
 #define SP_PIPE_WPS 3
 #endif
-// (experiment, off: -DSP_PIPE_DENSE treats every cell of a live offset as live — dead cells multiply the zero row — so that the
-// four cells of an iteration are one basic block; tools/profiling/k9d_shape_probe.hip says what the branch-free shape could reach)
-#ifdef SP_PIPE_DENSE
-#define SP_PIPE_LIVE(mask, g) (true)
-#else
+// (Treating every cell of a live offset as live — dead cells multiply the zero row, the four cells of an iteration are one basic
+// block — was measured and not kept: profiles/r6_k9d_dense_cells_experiment.txt; tools/profiling/k9d_shape_probe.hip says what the
+// branch-free shape could reach.)
 #define SP_PIPE_LIVE(mask, g) (((mask) >> (g)) & 1u)
-#endif
 template <int TPW, int NKC>
 __global__ void __launch_bounds__(256, SP_PIPE_WPS) spconv_fwd_pipe_kernel(SpArgs a) {
   using S = SpPipeSmem<TPW>;
@@ -793,11 +709,7 @@ __global__ void __launch_bounds__(256, SP_PIPE_WPS) spconv_fwd_pipe_kernel(SpArg
   const int nk = __builtin_amdgcn_readfirstlane(*nk_s);
   const int nsrc = a.c[1] > 0 ? 2 : 1;
   const int nchunks = NKC * nsrc;
-#ifdef PD_ABL_NO_LOOP
-  const int nsteps = 0;
-#else
   const int nsteps = nk * nsrc;
-#endif
   const float w_inv = a.w_hdr[0];
   const uint32_t rowbytes = (uint32_t)NKC * 128u;  // both sources are NKC * 32 channels wide
 
@@ -844,9 +756,6 @@ __global__ void __launch_bounds__(256, SP_PIPE_WPS) spconv_fwd_pipe_kernel(SpArg
     sc = (st.src ? a.sx[1] : a.sx[0])[is];
   };
   auto gather_chunk = [&](const SpStep& st, int kc, uint32_t off0, uint32_t off1, uint4& va, uint4& vb) {
-#ifdef PD_ABL_NO_G
-    return;
-#endif
     // (a dead cell's rows are fetched all the same: `if (!live) return` here measured 5-10 % SLOWER on every layer, 30 % on the
     // 256 -> 256 one — the branch keeps the compiler from hoisting the loads over the staging writes)
     const char* p = (st.src ? a.x[1] : a.x[0]) + (uint32_t)(kc * 128);
@@ -856,9 +765,6 @@ __global__ void __launch_bounds__(256, SP_PIPE_WPS) spconv_fwd_pipe_kernel(SpArg
   // LDS tile of one (slot, cell): 16 rows x 8 pieces x 16 B = 2 KB
   const int wr_a = grow * 8 + (gpiece ^ ((grow >> 1) & 7)), wr_b = (8 + grow) * 8 + (gpiece ^ (((8 + grow) >> 1) & 7));
   auto stage_to_lds = [&](const SpStep& st, int kc, int slot, int parity, const uint4& va, const uint4& vb, float sc) {
-#ifdef PD_ABL_NO_LDS_WRITE
-    return;
-#endif
     if SP_PIPE_LIVE(st.mask, wave) {
       uint4* dst = xring + (slot * RG + wave) * 128;
       dst[wr_a] = va;
@@ -868,9 +774,6 @@ __global__ void __launch_bounds__(256, SP_PIPE_WPS) spconv_fwd_pipe_kernel(SpArg
   };
   const int rd_hi = j * 8 + ((2 * sp_kgroup(q)) ^ ((j >> 1) & 7)), rd_lo = j * 8 + ((2 * sp_kgroup(q) + 1) ^ ((j >> 1) & 7));
   auto load_w = [&](const SpStep& st, int kc, uint4 (&wf)[TPW][2]) {
-#ifdef PD_ABL_NO_W
-    if (st.kidx > 0 || st.src > 0 || kc > 0) return;
-#endif
     const int c = (st.src ? NKC : 0) + kc;
     const uint4* p = reinterpret_cast<const uint4*>(a.w) + ((((int64_t)slice * kvol + st.k) * nchunks + c) * 4 + wave) * (TPW * 2 * 64) + lane;
 #pragma unroll
@@ -879,9 +782,6 @@ __global__ void __launch_bounds__(256, SP_PIPE_WPS) spconv_fwd_pipe_kernel(SpArg
       for (int pl = 0; pl < 2; ++pl) wf[t][pl] = p[(t * 2 + pl) * 64];
   };
   auto read_cell = [&](int slot, int g, uint4& xh, uint4& xl) {
-#ifdef PD_ABL_NO_LDS_READ
-    return;
-#endif
     const uint4* xs = xring + (slot * RG + g) * 128;
     xh = xs[rd_hi];
     xl = xs[rd_lo];
@@ -894,12 +794,6 @@ __global__ void __launch_bounds__(256, SP_PIPE_WPS) spconv_fwd_pipe_kernel(SpArg
       wh[t] = __builtin_bit_cast(sp_f16x8, wk[t][0]);
       wl[t] = __builtin_bit_cast(sp_f16x8, wk[t][1]);
     }
-#ifdef PD_ABL_NO_MFMA
-#pragma unroll
-    for (int t = 0; t < TPW; ++t)
-      D[g][t][0] = (first ? 0.0f : D[g][t][0]) + __uint_as_float(xh.x ^ wk[t][0].x ^ xl.y ^ wk[t][1].y);
-    return;
-#endif
 #pragma unroll
     for (int t = 0; t < TPW; ++t)
       D[g][t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wl[t], bh, first ? sp_f32x4{0.f, 0.f, 0.f, 0.f} : D[g][t], 0, 0, 0);
@@ -958,9 +852,7 @@ __global__ void __launch_bounds__(256, SP_PIPE_WPS) spconv_fwd_pipe_kernel(SpArg
     const SpStep st2 = d2 == 0 ? r0 : r1;
     const SpStep st3 = d3 == 0 ? r0 : (d3 == 1 ? r1 : r2);
     constexpr int kc1 = (KC + 1) % NKC, kc2 = (KC + 2) % NKC, kc3 = (KC + 3) % NKC;
-#ifndef PD_ABL_NO_BARRIER
     __syncthreads();
-#endif
     // staging of the chunks ahead
     stage_to_lds(st2, kc2, (I + 2) % 4, (ODD + d2) & 1, g_a, g_b, g_sc);
     if (kc3 == 0) gather_row(st3, g_off0, g_off1, g_sc);

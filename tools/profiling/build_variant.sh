@@ -1,6 +1,6 @@
 #!/bin/bash
 # usage (build container): tools/profiling/build_variant.sh <name> <source.hip> <hipcc flags...>  -> ab_prev/variants/libfsf_<name>.so :
-# the tree's library with ONE source recompiled under extra flags (an ablation / experiment build), for same-box A/Bs through FSF_LIB_PATH.
+# the tree's library with ONE source recompiled under extra flags (a compiler-flag or tuning-constant experiment build), for same-box A/Bs through FSF_LIB_PATH.
 set -e
 name=$1; src=$2; shift; shift
 cs=fullysparsefusion_amd/csrc
