@@ -23,7 +23,11 @@ launched by tools/dist_train.sh:8-9 with one process per GPU).  Differences that
     reduces the accumulated sum.  The buckets are cleared by `zero_grad()` — or by the optimizer's own
     `zero_grad()`: with `set_to_none=False` it zeroes the views in place, with `set_to_none=True` (torch's default) it drops
     `param.grad`, and the next forward / backward then zeroes that parameter's slice before re-pointing `param.grad` at it
-    (a dropped gradient means "cleared", never "resume from what the bucket last held").
+    (a dropped gradient means "cleared", never "resume from what the bucket last held");
+  * `optim.FusedAdamW.step(zero_grads=True)` (K39) steps straight on the buckets and stores 0 to every gradient element it has
+    consumed, so a loop that uses it does NOT call `zero_grad()`: `param.grad` stay the bucket views, the next forward's
+    `_arm(zero=False)` finds them in place and the next backward adds onto zeros.  It reads `buckets` (`params`, `views`, `flat`) and
+    changes nothing else here.
 """
 import contextlib
 

@@ -636,7 +636,51 @@ int fsf_frustum_assign(const float* cluster_xyz, int64_t n, int64_t xyz_stride, 
                        int32_t* source, float* stats, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
- * K13-K15  LiDAR -> camera projection + per-point instance-mask gather
+ * K39  optimizer step on the gradient buckets: global-norm gradient clip + AdamW + gradient clear (docs/kernels/K39_optimizer_step.md)
+ * Replaces mmcv's OptimizerHook.after_train_iter as the reference's schedules configure it (cyclic_20e.py, cosine_2x.py):
+ *   torch.nn.utils.clip_grad_norm_(params, max_norm, norm_type=2), torch.optim.AdamW.step(), optimizer.zero_grad().
+ * The chunk table (device, built once by the caller): num_chunks rows of FSF_OPTIM_TABLE_WORDS int64
+ *   [0] parameter address  [1] gradient address  [2] exp_avg address  [3] exp_avg_sq address  (f32 each, 4-byte aligned, device)
+ *   [4] low 32 bits: element count, 1 .. FSF_OPTIM_CHUNK; high 32 bits: group id, 0 .. num_groups - 1
+ *   The rows of one parameter follow each other FSF_OPTIM_CHUNK elements apart, so a parameter's rows share their alignment.  An
+ *   address that is 16-byte aligned is read and written 16 bytes at a time, any other one float at a time; which element a thread
+ *   takes and what it computes do not depend on that, so both forms give the same bits.
+ * fsf_optim_grad_sumsq (K39a): partial[w] = the float64 sum of g * g (each g widened first) over the chunks w, w + W, ... of workgroup
+ *   w, W = min(num_chunks, FSF_OPTIM_MAX_PARTIALS) workgroups; thread t of a chunk takes elements 4 (t + 256 k) .. + 3, k ascending,
+ *   and the 256 thread sums are added as a fixed tree.  No atomics, no ticket: the same bits on every run.
+ *   workspace: fsf_optim_workspace_bytes(num_chunks) = 8 W bytes, float64 [W]
+ * fsf_optim_adamw_step (K39b): one launch over every chunk.  With clip != 0 every workgroup first adds the W partials of K39a (thread t
+ *   takes t, t + 256, ..., then the same tree), and
+ *     norm = f32(sqrt(sum));  c = max_norm / (norm + 1e-6f);  coef = c > 1 ? 1 : c   (a NaN c stays NaN, an infinite norm gives 0)
+ *   workgroup 0 stores norm to grad_norm[0].  With clip == 0 the workspace is not read, coef = 1 exactly and grad_norm is not written.
+ *   Then per element, in f32, every operation rounded on its own (no fma), with w = one_minus_beta1 and G = the chunk's group id:
+ *     g = g_raw * coef
+ *     p = p * decay_factor[G]
+ *     m = w < 0.5 ? m + w * (g - m) : g - (g - m) * (1 - w)
+ *     v = v * beta2 + (one_minus_beta2 * g) * g
+ *     denom = sqrt(v) / bc2_sqrt + eps                     (sqrt and / correctly rounded)
+ *     p = p - step_size[G] * (m / denom)
+ *   p, m, v are stored back; with zero_grads != 0 the gradient element is then stored as 0, otherwise it is left as it was.
+ *   decay_factor / step_size are HOST arrays of num_groups floats: f32(1 - lr_G * weight_decay_G) and f32(lr_G / (1 - beta1^t)), which
+ *   the caller computes in double like beta2, one_minus_beta2, bc2_sqrt = f32(sqrt(1 - beta2^t)).  max_norm is not read with clip == 0.
+ *   num_chunks == 0 is FSF_OK without a launch (both entry points).  FSF_ERR_INVALID_ARG: num_chunks < 0, a NULL table, host array,
+ *   or (clip != 0) grad_norm / workspace with num_chunks > 0, num_groups < 1.  FSF_ERR_UNSUPPORTED: num_groups > FSF_OPTIM_MAX_GROUPS.
+ *   FSF_ERR_WORKSPACE: fewer than fsf_optim_workspace_bytes bytes.  No synchronisation, no atomics, no memset.
+ */
+#define FSF_OPTIM_CHUNK 4096        /* elements of one table row at most: 256 threads x 4 rounds of 4 elements */
+#define FSF_OPTIM_MAX_PARTIALS 1024 /* workgroups of K39a = float64 partials K39b adds up */
+#define FSF_OPTIM_MAX_GROUPS 8      /* distinct (learning rate, weight decay) pairs; the reference's configs produce 2 - 4 */
+#define FSF_OPTIM_TABLE_WORDS 5     /* int64 words of one table row */
+int64_t fsf_optim_table_bytes(int64_t num_chunks);
+int64_t fsf_optim_workspace_bytes(int64_t num_chunks);
+int fsf_optim_grad_sumsq(const int64_t* table, int64_t num_chunks, void* workspace, int64_t workspace_bytes, void* stream);
+int fsf_optim_adamw_step(const int64_t* table, int64_t num_chunks, int32_t num_groups, const float decay_factor[FSF_OPTIM_MAX_GROUPS],
+                         const float step_size[FSF_OPTIM_MAX_GROUPS], float one_minus_beta1, float beta2, float one_minus_beta2,
+                         float bc2_sqrt, float eps, float max_norm, int32_t clip, int32_t zero_grads, const void* workspace,
+                         int64_t workspace_bytes, float* grad_norm, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * K13-K15 LiDAR -> camera projection + per-point instance-mask gather
  * Replaces: FSF.prj_points_2d (projects/mmdet3d_plugin/models/detectors/FSF.py:169-200) and
  *   FSF.points_in_mask (:202-226) for one batch sample; the caller loops samples like frustum_gather (:228-258).
  * Gathers straight from the integer mask (no .float() copy, FSF.py:209); pixel =
