@@ -43,6 +43,9 @@ struct LnaArgs {
   // of fsf_to_planes with ONE power-of-two scale per row) —, x_inv_scale[row] = 1 / s_row, `planes` = f16 hi | lo fragments of
   // W * s_w behind a 256-byte header whose first float is 1 / s_w.  The product runs as three v_mfma_f32_16x16x32_f16 per
   // fp32-equivalent one (hi hi + hi lo + lo hi, as K9d), no split in the main loop.
+  // The scale rules of the f16 forms (what tests/product_budget.py derives the per-element floors from): x — K22h: one s_row per row over
+  // all k columns; K22f: per row, following the running maximum over the LNA_KC-column chunks (lna_xf_scale_split); W — K22f and K22h:
+  // ONE power-of-two scale s_w for the whole layer (s_w * max |w| in [2^13, 2^14), lna_prepare_f16_kernel), whatever the slice width.
   const float* x_inv_scale;
 };
 
