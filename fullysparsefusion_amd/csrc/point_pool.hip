@@ -88,7 +88,7 @@ __device__ __forceinline__ int pool_test(const PoolBox& k, float x, float y, flo
   const float dx = x - k.cx, dy = y - k.cy;
   if (dx * dx + dy * dy > k.r2) return 0;  // rejects almost every pair: keep it first
   lz = z - k.cz;
-  if (fabsf(lz) > k.lhh) return 0;
+  if (!(fabsf(lz) <= k.lhh)) return 0;  // (written so that a NaN z is outside, as NaN x / y are below)
   lx = dx * k.cosa + dy * (-k.sina);
   ly = dx * k.sina + dy * k.cosa;
   const bool in_large = (lx > -k.lhl) & (lx < k.lhl) & (ly > -k.lhw) & (ly < k.lhw);

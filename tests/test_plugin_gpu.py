@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 import torch
 
+import pool_cases
 from conftest import build_test_fsf, golden_cases, load_golden, param_checksum
 from oracle import modules as omod
 from oracle import scatter as oscatter
@@ -700,16 +701,17 @@ def test_refine_head_vs_oracle(plugin, device):
     near = rois[which, 1:4] + rng.normal(0, 1.2, (p // 2, 3)) + np.array([0, 0, 1.0])
     pts = np.concatenate([near, np.concatenate([rng.uniform(-35, 35, (p - p // 2, 2)), rng.uniform(-3, 1, (p - p // 2, 1))], 1)])
     pts = np.concatenate([pts, rng.random((p, 2))], 1).astype(np.float32)
+    pts[:, :3], parked, _ = pool_cases.margin_clean(rois[:, 1:], pts[:, :3], [1.0, 1.0, 1.0])  # no pair within 1e-3 of a face
+    assert parked.size <= 0.02 * p
     feats = rng.standard_normal((p, 40)).astype(np.float32)
 
     ext = plugin.registry.build_roi_extractor(dict(type="DynamicPointROIExtractor", extra_wlh=[1.0, 1.0, 1.0], max_inbox_point=512,
                                                    debug=True))
     d_pts, d_rois = torch.from_numpy(pts).to(device), torch.from_numpy(rois).to(device)
     inds, roi_inds, info = ext(d_pts[:, :3], torch.zeros(p, dtype=torch.long, device=device), d_rois)
-    wp, wr, wf, margins = orefine.dynamic_point_pool(rois[:, 1:], pts[:, :3], [1.0, 1.0, 1.0], 512, return_margin=True)
-    if (margins[:, 2] < 1e-4).sum() == 0:
-        np.testing.assert_array_equal(inds.cpu().numpy(), wp)
-        np.testing.assert_array_equal(roi_inds.cpu().numpy(), wr)
+    wp, wr, wf = orefine.dynamic_point_pool(rois[:, 1:], pts[:, :3], [1.0, 1.0, 1.0], 512)
+    np.testing.assert_array_equal(inds.cpu().numpy(), wp)
+    np.testing.assert_array_equal(roi_inds.cpu().numpy(), wr)
     with torch.no_grad():
         out, mask = head(d_pts[inds], torch.from_numpy(feats).to(device)[inds], info, roi_inds, d_rois)
         # the groups indexed by RoI directly (default) and through a unique + scatter: the same rows, bit for bit
