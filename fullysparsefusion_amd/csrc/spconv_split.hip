@@ -511,6 +511,34 @@ extern "C" int fsf_spconv_prepare_weight_split(const float* weight, int32_t kvol
   return FSF_OK;
 }
 
+// The host launch path of both forward entry points (K9b: T = 4 | 8 on fp32 rows; K9b-XP: T = 8 on plane rows): `a` comes with the
+// operands and shapes, validated by the caller, with `partial` = the caller's workspace; the split of the chunk sequence, the grid
+// and its XCD-aware layout, the LDS size and the fold pass are decided here.
+template <int T, bool XP>
+static int scs_launch(ScsArgs a, int64_t workspace_bytes, hipStream_t stream) {
+  a.ksplit = scs_ksplit(a.m_out, a.cin, a.cout, a.kvol);
+  if (a.ksplit > 1 && (!a.partial || workspace_bytes < fsf_spconv_split_workspace_bytes(a.m_out, a.cin, a.cout, a.kvol)))
+    return FSF_ERR_WORKSPACE;
+  const int64_t nblk = (a.m_out + SCS_ROWS - 1) / SCS_ROWS;
+  const int nslice = scs_slices(a.cout), groups = nslice * a.ksplit;
+  int64_t gx = (256 * SCS_WPS + groups - 1) / groups;
+  if (gx > nblk) gx = nblk;
+  dim3 grid((unsigned)gx, (unsigned)nslice, (unsigned)a.ksplit);
+  if (gx > 1 && groups >= 8) {  // several row blocks stream the same chunks and there are groups for every XCD
+    a.xcd_lanes = (int)gx;
+    a.nslice = nslice;
+    grid = dim3((unsigned)(8 * gx * ((groups + 7) / 8)), 1, 1);
+  }
+  constexpr size_t smem = (size_t)2 * T * (XP ? 2 : 3) * 64 * 16 + 1024;
+  static std::atomic<uint64_t> attr_done{0};
+  FSF_HIP_TRY(fsf_set_max_dynamic_lds((const void*)spconv_fwd_split_kernel<T, XP>, (int)smem, attr_done));
+  hipLaunchKernelGGL((spconv_fwd_split_kernel<T, XP>), grid, dim3(SCS_NW * 64), smem, stream, a);
+  if (a.ksplit > 1)
+    hipLaunchKernelGGL(scs_fold_kernel, dim3(fsf_stream_grid(a.m_out * (a.cout / 4), 256)), dim3(256), 0, stream, a);
+  FSF_LAUNCH_CHECK();
+  return FSF_OK;
+}
+
 extern "C" int fsf_spconv_forward_split(const float* feat, int64_t m_in, int32_t cin, const void* planes, int32_t kvol,
                                         int32_t cout, const int32_t* nbr, int64_t m_out, const float* scale,
                                         const float* shift, const float* residual, int32_t relu, float* out, void* workspace,
@@ -522,34 +550,9 @@ extern "C" int fsf_spconv_forward_split(const float* feat, int64_t m_in, int32_t
   if ((cin % 4) != 0 || (cout % 4) != 0 || ((uintptr_t)feat % 16) != 0 || ((uintptr_t)out % 16) != 0) return FSF_ERR_UNSUPPORTED;
   if (m_out == 0) return FSF_OK;
   if (m_in == 0) return FSF_ERR_INVALID_ARG;  // (a missing neighbour reads row 0)
-  const int ksplit = scs_ksplit(m_out, cin, cout, kvol);
-  if (ksplit > 1 && (!workspace || workspace_bytes < fsf_spconv_split_workspace_bytes(m_out, cin, cout, kvol))) return FSF_ERR_WORKSPACE;
   ScsArgs a{feat, (const uint4*)planes, nbr, scale, shift, residual, out, (float*)workspace, m_in, m_out,
-            (int)cin, (int)cout, (int)kvol, (int)relu, ksplit, 0, 0, nullptr};
-  const int64_t nblk = (m_out + SCS_ROWS - 1) / SCS_ROWS;
-  const int nslice = scs_slices(cout);
-  int64_t gx = (256 * SCS_WPS + nslice * ksplit - 1) / (nslice * ksplit);
-  if (gx > nblk) gx = nblk;
-  dim3 grid((unsigned)gx, (unsigned)nslice, (unsigned)ksplit);
-  if (gx > 1 && nslice * ksplit >= 8) {  // several row blocks stream the same chunks and there are groups for every XCD
-    a.xcd_lanes = (int)gx;
-    a.nslice = nslice;
-    grid = dim3((unsigned)(8 * gx * ((nslice * ksplit + 7) / 8)), 1, 1);
-  }
-#define FSF_SCS(T_)                                                                                                     \
-  do {                                                                                                                 \
-    constexpr size_t smem = (size_t)2 * T_ * 3 * 64 * 16 + 1024;                                                       \
-    static std::atomic<uint64_t> attr_done{0};                                                                                      \
-    FSF_HIP_TRY(fsf_set_max_dynamic_lds((const void*)spconv_fwd_split_kernel<T_>, (int)smem, attr_done));                                                                                                                  \
-    hipLaunchKernelGGL((spconv_fwd_split_kernel<T_>), grid, dim3(SCS_NW * 64), smem, stream, a);                       \
-  } while (0)
-  if (scs_tiles(cout) == 4) FSF_SCS(4);
-  else FSF_SCS(8);
-#undef FSF_SCS
-  if (ksplit > 1)
-    hipLaunchKernelGGL(scs_fold_kernel, dim3(fsf_stream_grid(m_out * (cout / 4), 256)), dim3(256), 0, stream, a);
-  FSF_LAUNCH_CHECK();
-  return FSF_OK;
+            (int)cin, (int)cout, (int)kvol, (int)relu, 0, 0, 0, nullptr};
+  return scs_tiles(cout) == 4 ? scs_launch<4, false>(a, workspace_bytes, stream) : scs_launch<8, false>(a, workspace_bytes, stream);
 }
 
 // ---- K9b-XP entry points -----------------------------------------------------------------------------------------------------
@@ -591,25 +594,7 @@ extern "C" int fsf_spconv_forward_split_planes(const void* feat_planes, const fl
     return FSF_ERR_UNSUPPORTED;
   if (m_out == 0) return FSF_OK;
   if (m_in == 0) return FSF_ERR_INVALID_ARG;
-  const int ksplit = scs_ksplit(m_out, cin, cout, kvol);
-  if (ksplit > 1 && (!workspace || workspace_bytes < fsf_spconv_split_workspace_bytes(m_out, cin, cout, kvol))) return FSF_ERR_WORKSPACE;
   ScsArgs a{(const float*)feat_planes, (const uint4*)planes, nbr, scale, shift, residual, out, (float*)workspace, m_in, m_out,
-            (int)cin, (int)cout, (int)kvol, (int)relu, ksplit, 0, 0, feat_inv_scales};
-  const int64_t nblk = (m_out + SCS_ROWS - 1) / SCS_ROWS;
-  const int nslice = scs_slices(cout);
-  int64_t gx = (256 * SCS_WPS + nslice * ksplit - 1) / (nslice * ksplit);
-  if (gx > nblk) gx = nblk;
-  dim3 grid((unsigned)gx, (unsigned)nslice, (unsigned)ksplit);
-  if (gx > 1 && nslice * ksplit >= 8) {
-    a.xcd_lanes = (int)gx;
-    a.nslice = nslice;
-    grid = dim3((unsigned)(8 * gx * ((nslice * ksplit + 7) / 8)), 1, 1);
-  }
-  constexpr size_t smem = (size_t)2 * 8 * 2 * 64 * 16 + 1024;
-  static std::atomic<uint64_t> attr_done{0};
-  FSF_HIP_TRY(fsf_set_max_dynamic_lds((const void*)spconv_fwd_split_kernel<8, true>, (int)smem, attr_done));
-  hipLaunchKernelGGL((spconv_fwd_split_kernel<8, true>), grid, dim3(SCS_NW * 64), smem, stream, a);
-  if (ksplit > 1) hipLaunchKernelGGL(scs_fold_kernel, dim3(fsf_stream_grid(m_out * (cout / 4), 256)), dim3(256), 0, stream, a);
-  FSF_LAUNCH_CHECK();
-  return FSF_OK;
+            (int)cin, (int)cout, (int)kvol, (int)relu, 0, 0, 0, feat_inv_scales};
+  return scs_launch<8, true>(a, workspace_bytes, stream);
 }

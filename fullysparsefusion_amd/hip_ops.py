@@ -903,6 +903,25 @@ def rulebook_to_pairs(nbr: torch.Tensor):
 
 
 # --------------------------------------------------------------------------------------- sparse conv
+def _epilogue(scale, shift, residual, m_out, cout):
+    """The fused epilogue's operands as every spconv_forward* entry reads them: on the device, contiguous, residual [m_out, cout]."""
+    require_cuda(scale, shift, residual)
+    scale, shift, residual = (t.contiguous() if t is not None else None for t in (scale, shift, residual))
+    assert residual is None or residual.shape == (m_out, cout)
+    return scale, shift, residual
+
+
+def _prepare_weight(weight, nbytes, entry):
+    """spconv v1 weight f32 [kvol, cin, cout] -> the u8 buffer of `nbytes`(kvol, cin, cout) bytes that the library's `entry` fills."""
+    require_cuda(weight)
+    weight = weight.detach().contiguous()
+    kvol, cin, cout = weight.shape
+    h = _L()
+    planes = torch.empty(getattr(h, nbytes)(kvol, cin, cout), dtype=torch.uint8, device=weight.device)
+    check(getattr(h, entry)(ptr(weight), kvol, cin, cout, ptr(planes), stream_ptr()), entry)
+    return planes
+
+
 def spconv_transpose_weight(weight: torch.Tensor):
     """weight f32 [kvol, cin, cout] (spconv v1 layout flattened) -> [kvol, cout, cin]."""
     require_cuda(weight)
@@ -926,13 +945,7 @@ def spconv_forward(feat: torch.Tensor, weight_t: torch.Tensor, nbr: torch.Tensor
     assert cin_w == cin and nbr.size(1) == kvol and nbr.dtype == torch.int32
     m_out = nbr.size(0)
     out = torch.empty((m_out, cout), dtype=torch.float32, device=feat.device)
-    if scale is not None:
-        scale = scale.contiguous()
-    if shift is not None:
-        shift = shift.contiguous()
-    if residual is not None:
-        residual = residual.contiguous()
-        assert residual.shape == out.shape
+    scale, shift, residual = _epilogue(scale, shift, residual, m_out, cout)
     h = _L()
     ws = _lib.workspace(h.fsf_spconv_workspace_bytes(m_out, cin, cout, kvol), feat.device)
     check(h.fsf_spconv_forward(ptr(feat), m_in, cin, ptr(weight_t), kvol, cout, ptr(nbr), m_out, ptr(scale), ptr(shift),
@@ -943,14 +956,7 @@ def spconv_forward(feat: torch.Tensor, weight_t: torch.Tensor, nbr: torch.Tensor
 
 def spconv_prepare_weight_split(weight: torch.Tensor):
     """fsf_spconv_prepare_weight_split: spconv v1 weight f32 [kvol, cin, cout] -> opaque split-bf16 fragment planes."""
-    require_cuda(weight)
-    weight = weight.detach().contiguous()
-    kvol, cin, cout = weight.shape
-    h = _L()
-    planes = torch.empty(h.fsf_spconv_split_weight_bytes(kvol, cin, cout), dtype=torch.uint8, device=weight.device)
-    check(h.fsf_spconv_prepare_weight_split(ptr(weight), kvol, cin, cout, ptr(planes), stream_ptr()),
-          "fsf_spconv_prepare_weight_split")
-    return planes
+    return _prepare_weight(weight, "fsf_spconv_split_weight_bytes", "fsf_spconv_prepare_weight_split")
 
 
 def spconv_forward_split(feat: torch.Tensor, planes: torch.Tensor, kvol: int, cout: int, nbr: torch.Tensor, scale=None,
@@ -963,11 +969,7 @@ def spconv_forward_split(feat: torch.Tensor, planes: torch.Tensor, kvol: int, co
     assert nbr.size(1) == kvol and nbr.dtype == torch.int32
     m_out = nbr.size(0)
     out = torch.empty((m_out, cout), dtype=torch.float32, device=feat.device)
-    scale = scale.contiguous() if scale is not None else None
-    shift = shift.contiguous() if shift is not None else None
-    if residual is not None:
-        residual = residual.contiguous()
-        assert residual.shape == out.shape
+    scale, shift, residual = _epilogue(scale, shift, residual, m_out, cout)
     h = _L()
     ws = _lib.workspace(h.fsf_spconv_split_workspace_bytes(m_out, cin, cout, kvol), feat.device)
     check(h.fsf_spconv_forward_split(ptr(feat), m_in, cin, ptr(planes), kvol, cout, ptr(nbr), m_out, ptr(scale), ptr(shift),
@@ -978,14 +980,7 @@ def spconv_forward_split(feat: torch.Tensor, planes: torch.Tensor, kvol: int, co
 
 def spconv_prepare_weight_split_f16(weight: torch.Tensor):
     """fsf_spconv_prepare_weight_split_f16: spconv v1 weight f32 [kvol, cin, cout] -> header + f16 hi | lo fragment planes (K9b-XP)."""
-    require_cuda(weight)
-    weight = weight.detach().contiguous()
-    kvol, cin, cout = weight.shape
-    h = _L()
-    planes = torch.empty(h.fsf_spconv_split_weight_f16_bytes(kvol, cin, cout), dtype=torch.uint8, device=weight.device)
-    check(h.fsf_spconv_prepare_weight_split_f16(ptr(weight), kvol, cin, cout, ptr(planes), stream_ptr()),
-          "fsf_spconv_prepare_weight_split_f16")
-    return planes
+    return _prepare_weight(weight, "fsf_spconv_split_weight_f16_bytes", "fsf_spconv_prepare_weight_split_f16")
 
 
 def spconv_split_planes_supported(cin: int, cout: int) -> bool:
@@ -996,16 +991,12 @@ def spconv_forward_split_planes(xp, planes: torch.Tensor, kvol: int, cout: int, 
                                 residual=None, relu=False):
     """fsf_spconv_forward_split_planes (K9b-XP): xp = RowPlanes of the input rows (rows_to_planes), planes from
     spconv_prepare_weight_split_f16, nbr i32 [m_out, kvol] -> out f32 [m_out, cout]."""
-    require_cuda(xp.data, planes, nbr, scale, shift, residual)
+    require_cuda(xp.data, planes, nbr)
     nbr = nbr.contiguous()
     assert nbr.size(1) == kvol and nbr.dtype == torch.int32
     m_in, cin, m_out = xp.n, xp.c, nbr.size(0)
     out = torch.empty((m_out, cout), dtype=torch.float32, device=nbr.device)
-    scale = scale.contiguous() if scale is not None else None
-    shift = shift.contiguous() if shift is not None else None
-    if residual is not None:
-        residual = residual.contiguous()
-        assert residual.shape == (m_out, cout)
+    scale, shift, residual = _epilogue(scale, shift, residual, m_out, cout)
     h = _L()
     ws = _lib.workspace(h.fsf_spconv_split_workspace_bytes(m_out, cin, cout, kvol), nbr.device)
     check(h.fsf_spconv_forward_split_planes(ptr(xp.data), ptr(xp.inv_scales), m_in, cin, ptr(planes), kvol, cout, ptr(nbr), m_out,
@@ -1055,14 +1046,7 @@ def to_planes(feat: torch.Tensor, row_index: Optional[torch.Tensor] = None) -> P
 
 def spconv_prepare_weight_planes(weight: torch.Tensor):
     """fsf_spconv_prepare_weight_planes: spconv v1 weight f32 [kvol, cin, cout] -> opaque f16 fragment planes (K9c)."""
-    require_cuda(weight)
-    weight = weight.detach().contiguous()
-    kvol, cin, cout = weight.shape
-    h = _L()
-    planes = torch.empty(h.fsf_spconv_planes_weight_bytes(kvol, cin, cout), dtype=torch.uint8, device=weight.device)
-    check(h.fsf_spconv_prepare_weight_planes(ptr(weight), kvol, cin, cout, ptr(planes), stream_ptr()),
-          "fsf_spconv_prepare_weight_planes")
-    return planes
+    return _prepare_weight(weight, "fsf_spconv_planes_weight_bytes", "fsf_spconv_prepare_weight_planes")
 
 
 def spconv_planes_supported(cins, cout: int, kvol: int) -> bool:
@@ -1075,7 +1059,7 @@ def spconv_forward_planes(sources, wplanes: torch.Tensor, kvol: int, cout: int, 
                           residual=None, relu=False, want_out=True, want_planes=False):
     """fsf_spconv_forward_planes (K9c): `sources` = [Planes] or [Planes, Planes] (channel concatenation), wplanes from
     spconv_prepare_weight_planes, nbr i32 [m_out, kvol] -> (out f32 [m_out, cout] or None, Planes of the output or None)."""
-    require_cuda(wplanes, nbr, scale, shift, residual)
+    require_cuda(wplanes, nbr)
     nbr = nbr.contiguous()
     assert nbr.size(1) == kvol and nbr.dtype == torch.int32 and 1 <= len(sources) <= 2 and (want_out or want_planes)
     a = sources[0]
@@ -1085,11 +1069,7 @@ def spconv_forward_planes(sources, wplanes: torch.Tensor, kvol: int, cout: int, 
     dev = nbr.device
     out = torch.empty((m_out, cout), dtype=torch.float32, device=dev) if want_out else None
     op = planes_empty(m_out, cout, dev) if want_planes else None
-    scale = scale.contiguous() if scale is not None else None
-    shift = shift.contiguous() if shift is not None else None
-    if residual is not None:
-        residual = residual.contiguous()
-        assert residual.shape == (m_out, cout)
+    scale, shift, residual = _epilogue(scale, shift, residual, m_out, cout)
     check(_L().fsf_spconv_forward_planes(ptr(a.data), ptr(a.scales), a.c, ptr(b.data) if b else c_p(None),
                                          ptr(b.scales) if b else c_p(None), b.c if b else 0, m_in, ptr(wplanes), kvol, cout,
                                          ptr(nbr), m_out, ptr(scale), ptr(shift), ptr(residual), int(bool(relu)), ptr(out),

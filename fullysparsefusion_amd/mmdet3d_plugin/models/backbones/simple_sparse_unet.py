@@ -126,9 +126,7 @@ class SimpleSparseUNet(nn.Module):
                 and hip_ops.channel_pair_sum_add2_supported(f_bot, f_lat)):
             up = upsample_layer[0]
             add = x_merge.features
-            if (switches.PLANES and f_bot.size(1) % 16 == 0 and f_lat.size(1) % 16 == 0 and f_bot.size(0) >= up.PLANES_MIN_ROWS
-                    and getattr(up, "in_channels", 0) == cout and hip_ops.spconv_planes_supported([cout], up.out_channels, 27)
-                    and up.kernel_size == [3, 3, 3]):
+            if f_bot.size(1) % 16 == 0 and f_lat.size(1) % 16 == 0 and up.takes_planes([cout], f_bot.size(0)):
                 # the sums' only reader is this level's upsampling convolution on K9d: they leave as planes (one launch instead of
                 # sum + fsf_to_planes, the fp32 rows never written); anything that asks for `.features` gets them formed then
                 y = x._like(None)
@@ -367,9 +365,8 @@ class SimpleSparseUNet(nn.Module):
         if perm64 is None:
             return SparseConvTensor(voxel_features, coors, self.sparse_shape, batch_size)
         conv = self.conv_input[0]
-        if (switches.PLANES and voxel_features.is_cuda and voxel_features.dtype == torch.float32 and not torch.is_grad_enabled()
-                and voxel_features.size(0) >= conv.PLANES_MIN_ROWS and conv.subm and conv.in_channels <= 128 and conv.in_channels % 32 == 0
-                and voxel_features.size(1) == conv.in_channels and hip_ops.spconv_planes_supported([conv.in_channels], conv.out_channels, 27)):
+        if (voxel_features.is_cuda and voxel_features.dtype == torch.float32 and not torch.is_grad_enabled() and conv.subm
+                and conv.takes_planes([voxel_features.size(1)], voxel_features.size(0))):
             x = SparseConvTensor(None, coors, self.sparse_shape, batch_size)
             x.plane_sources = [hip_ops.to_planes(voxel_features, row_index=perm64)]
             x.features_thunk = lambda: voxel_features.index_select(0, perm64)

@@ -107,25 +107,75 @@ class Rulebook:
         return self._pairs[inverse]
 
 
+def source_widths(cin):
+    """The plane-source widths of `cin` channels: up to 128 is one source, wider is the concatenation of two halves."""
+    return [cin] if cin <= 128 else [cin // 2, cin - cin // 2]
+
+
 def _plane_srcs(feat):
-    """fp32 rows -> K9c plane sources (<= 128 channels each; a wider tensor is the concatenation of its two halves)."""
-    c = feat.size(1)
-    if c <= 128:
-        return [hip_ops.to_planes(feat)]
-    return [hip_ops.to_planes(feat[:, :c // 2]), hip_ops.to_planes(feat[:, c // 2:])]
+    """The plane sources (hip_ops.Planes) of an fp32 matrix, one per width of `source_widths`."""
+    return [hip_ops.to_planes(f) for f in feat.split(source_widths(feat.size(1)), dim=1)]
 
 
-def _planes_shape_ok(cin, cout, kvol, rows):
-    cins = [cin] if cin <= 128 else [cin // 2, cin - cin // 2]
-    return rows >= SparseConvolution.PLANES_MIN_ROWS and hip_ops.spconv_planes_supported(cins, cout, kvol)
+# ---- which forward kernel runs a layer ----------------------------------------------------------------------------------------
+# THE rules; inference, the autograd function (both directions) and the U-Net's plane-form producers all ask `choose_kernel`.
+#   * no input rows or no table rows: "fp32" (nothing is launched).
+#   * "planes" (K9c / K9d, pre-split f16 planes with cell skipping; measured per layer, tools/profiling/planes_layers.py): the kernel
+#     only sees a neighbour table, so submanifold, strided and inverse layers alike — with switches.PLANES, from PLANES_MIN_ROWS table
+#     rows (below ~4 k the launch does not fill the chip and K9b's offset splits win), for plane sources whose widths sum to cin (the
+#     ones at hand, else `source_widths(cin)`) in a shape hip_ops.spconv_planes_supported takes.
+#   * "split" (K9b, row-stationary bf16 split; tools/profiling/scs_layers.py): both channel counts divisible by 4, on every
+#     submanifold layer (dense neighbourhoods: 1.15-1.7x on the fine levels, 1.5-2x on the deep ones, where it splits the offset loop
+#     over more workgroups) and on the strided convolutions into the deep levels (<= SPLIT_STRIDED_MAX_ROWS table rows: 13+ pairs per
+#     output row); "split_f16" (K9b-XP, both operands as f16 planes) in its place from 256 input channels (measured at 256 .. 1024;
+#     below, the conversion is the gain) where hip_ops.spconv_split_planes_supported — the caller also needs
+#     hip_ops.rows_to_planes_supported(feat), which depends on the tensor.
+#   * "fp32" (the compacting fp32-pipe kernel) otherwise: inverse convolutions, the strided ones into the fine levels (3-9 pairs per
+#     output row), channel counts that divide no tile.
+#   * the autograd path (`train`): planes only with switches.TRAIN_PLANES too, always on a conversion of the operand (the sources at
+#     hand are not looked at); split on submanifold layers only, never split_f16.  The data gradient is the same question with
+#     cin / cout swapped and the transposed table's row count (a submanifold table is its own transpose).
+PLANES, SPLIT_F16, SPLIT, FP32 = "planes", "split_f16", "split", "fp32"
+
+
+def choose_kernel(kind, cin, cout, kvol, rows, in_rows, src_widths=None, train=False, planes_on=True, train_planes_on=True,
+                  split_on=True):
+    """kind "subm" | "strided" | "inverse"; rows = rows of the table that is iterated, in_rows = rows of the operand; src_widths =
+    widths of the plane sources at hand (None: none); planes_on / train_planes_on = switches.PLANES / TRAIN_PLANES; split_on=False
+    is a caller's veto of the split kernels (`_SparseConvFn`'s `split` argument).  Plain values in, one of the four names out."""
+    if rows == 0 or in_rows == 0:
+        return FP32
+    widths = source_widths(cin) if train or src_widths is None else list(src_widths)
+    if (planes_on and (train_planes_on or not train) and rows >= SparseConvolution.PLANES_MIN_ROWS and sum(widths) == cin
+            and hip_ops.spconv_planes_supported(widths, cout, kvol)):
+        return PLANES
+    if split_on and cin % 4 == 0 and cout % 4 == 0 and (
+            kind == "subm" or (not train and kind == "strided" and rows <= SparseConvolution.SPLIT_STRIDED_MAX_ROWS)):
+        return SPLIT_F16 if not train and cin >= 256 and hip_ops.spconv_split_planes_supported(cin, cout) else SPLIT
+    return FP32
 
 
 class _SparseConvFn(torch.autograd.Function):
     """out = sum_k feat[table[:, k]] @ W[k] with the K10 backward: data gradient = the same fused kernel over the
-    transposed table, weight gradient = fsf_spconv_backward_weight over the pair lists.  `split` picks the
-    row-stationary split-bf16 kernel (K9b, fp32-accurate) for the forward and the data gradient, as in inference;
-    `planes` the f16-plane kernel (K9c) wherever the direction's shape is one it takes (the operand — features forward,
-    grad_out backward — is converted by fsf_to_planes, the weights of the step by fsf_spconv_prepare_weight_planes)."""
+    transposed table, weight gradient = fsf_spconv_backward_weight over the pair lists.  `split` allows the
+    row-stationary split-bf16 kernel (K9b, fp32-accurate) for the forward and the data gradient, `planes` the f16-plane kernel
+    (K9c; the operand — features forward, grad_out backward — is converted by fsf_to_planes, the weights of the step by
+    fsf_spconv_prepare_weight_planes).  Which of the allowed kernels a direction gets is `choose_kernel`'s answer for the autograd
+    path."""
+
+    @staticmethod
+    def _run(ctx, operand, w, w_is_t, table, kind):
+        """sum_k operand[table[:, k]] @ W[k] on the kernel `choose_kernel` names for this direction; w = W [kvol, cin, cout], or with
+        `w_is_t` its transpose [kvol, cout, cin] (the data gradient's: the form the fp32 kernel reads)."""
+        kvol, cin, cout = (w.size(0), w.size(2), w.size(1)) if w_is_t else w.shape
+        variant = choose_kernel(kind, cin, cout, kvol, table.size(0), operand.size(0), train=True, planes_on=ctx.planes,
+                                train_planes_on=ctx.planes, split_on=ctx.split)
+        if variant == FP32:
+            return hip_ops.spconv_forward(operand, w if w_is_t else hip_ops.spconv_transpose_weight(w), table)
+        w = w.transpose(1, 2).contiguous() if w_is_t else w
+        if variant == PLANES:
+            return hip_ops.spconv_forward_planes(_plane_srcs(operand), hip_ops.spconv_prepare_weight_planes(w), kvol, cout, table)[0]
+        return hip_ops.spconv_forward_split(operand, hip_ops.spconv_prepare_weight_split(w), kvol, cout, table)
 
     @staticmethod
     def forward(ctx, feat, weight, rb, inverse, split, planes=False):
@@ -133,12 +183,7 @@ class _SparseConvFn(torch.autograd.Function):
         w = weight.detach().reshape(kvol, weight.shape[-2], weight.shape[-1])
         ctx.rb, ctx.inverse, ctx.split, ctx.planes = rb, inverse, split, planes
         ctx.save_for_backward(feat, weight)
-        table = rb.table(inverse)
-        if planes and feat.size(0) > 0 and _planes_shape_ok(w.size(1), w.size(2), kvol, table.size(0)):
-            return hip_ops.spconv_forward_planes(_plane_srcs(feat), hip_ops.spconv_prepare_weight_planes(w), kvol, w.size(2), table)[0]
-        if split and feat.size(0) > 0:
-            return hip_ops.spconv_forward_split(feat, hip_ops.spconv_prepare_weight_split(w), kvol, w.size(2), table)
-        return hip_ops.spconv_forward(feat, hip_ops.spconv_transpose_weight(w), table)
+        return _SparseConvFn._run(ctx, feat, w, False, rb.table(inverse), "inverse" if inverse else rb.kind)
 
     @staticmethod
     def backward(ctx, grad):
@@ -151,15 +196,7 @@ class _SparseConvFn(torch.autograd.Function):
             table_t, flip = rb.table_transposed(inverse)
             w = weight.detach().reshape(kvol, weight.shape[-2], weight.shape[-1])
             w = w.flip(0) if flip else w
-            if (ctx.planes and grad.size(0) > 0 and feat.size(0) > 0
-                    and _planes_shape_ok(w.size(2), w.size(1), kvol, table_t.size(0))):
-                wt = hip_ops.spconv_prepare_weight_planes(w.transpose(1, 2).contiguous())
-                g_feat = hip_ops.spconv_forward_planes(_plane_srcs(grad), wt, kvol, w.size(1), table_t)[0]
-            elif ctx.split and grad.size(0) > 0 and feat.size(0) > 0:
-                planes = hip_ops.spconv_prepare_weight_split(w.transpose(1, 2).contiguous())
-                g_feat = hip_ops.spconv_forward_split(grad, planes, kvol, w.size(1), table_t)
-            else:
-                g_feat = hip_ops.spconv_forward(grad, w, table_t)
+            g_feat = _SparseConvFn._run(ctx, grad, w, True, table_t, "inverse" if inverse else rb.kind)
         if ctx.needs_input_grad[1]:
             pairs, num = rb.pairs(inverse)
             g_w = hip_ops.spconv_backward_weight(feat, grad, pairs, num).reshape(weight.shape)
@@ -191,7 +228,7 @@ class SparseConvolution(SparseModule):
             self.bias = nn.Parameter(torch.empty(out_channels))
         else:
             self.register_parameter("bias", None)
-        self._wt_cache = None
+        self._prepared_cache = {}  # kernel name -> (weight key, prepared weights): plain data, no parameter / buffer / state_dict entry
         self.reset_parameters()
 
     def reset_parameters(self):
@@ -235,86 +272,42 @@ class SparseConvolution(SparseModule):
             x.indice_dict[self.indice_key] = rb
         return rb
 
-    def _weight_t(self):
-        w = self.weight
-        key = (w._version, w.data_ptr())
-        if self._wt_cache is None or self._wt_cache[0] != key:
-            kvol = math.prod(self.kernel_size)
-            wt = hip_ops.spconv_transpose_weight(w.detach().reshape(kvol, self.in_channels, self.out_channels))
-            self._wt_cache = (key, wt)
-        return self._wt_cache[1]
-
-    # Which forward kernel (measured per layer on the 10-sweep frame, tools/profiling/scs_layers.py): the row-stationary
-    # bf16-split kernel (K9b) wins on every submanifold layer (dense neighbourhoods: 1.15-1.7x on the fine levels,
-    # 1.5-2x on the deep ones, where it splits the offset loop over more workgroups) and on the strided convolutions
-    # into the deep levels (13+ pairs per output row); inverse convolutions and the strided ones into the fine levels
-    # (3-9 pairs per output row) stay on the compacting fp32-pipe kernel.
+    # tuning constants of `choose_kernel` (read there at call time)
     SPLIT_STRIDED_MAX_ROWS = 10000
-
-    def _use_split_kernel(self, m_out):
-        if self.in_channels % 4 or self.out_channels % 4:
-            return False
-        return self.subm or (not self.inverse and m_out <= self.SPLIT_STRIDED_MAX_ROWS)
-
-    def _use_split_kernel_training(self):
-        """Training uses K9b for the forward AND the data gradient of the submanifold layers (their transposed table
-        has the same row count); strided / inverse layers keep the compacting fp32 kernel in both directions."""
-        return self.subm and self.in_channels % 4 == 0 and self.out_channels % 4 == 0
-
-    def _weight_split(self):
-        w = self.weight
-        key = (w._version, w.data_ptr())
-        cache = self.__dict__.get("_wsplit_cache")
-        if cache is None or cache[0] != key:
-            kvol = math.prod(self.kernel_size)
-            cache = (key, hip_ops.spconv_prepare_weight_split(w.detach().reshape(kvol, self.in_channels, self.out_channels)))
-            self.__dict__["_wsplit_cache"] = cache
-        return cache[1]
-
-    def _weight_split_f16(self):
-        w = self.weight
-        key = (w._version, w.data_ptr())
-        cache = self.__dict__.get("_wsplit16_cache")
-        if cache is None or cache[0] != key:
-            kvol = math.prod(self.kernel_size)
-            cache = (key, hip_ops.spconv_prepare_weight_split_f16(w.detach().reshape(kvol, self.in_channels, self.out_channels)))
-            self.__dict__["_wsplit16_cache"] = cache
-        return cache[1]
-
-    # K9c (pre-split f16 planes, cell skipping): every layer whose sources are <= 128 channels wide — submanifold, strided and
-    # inverse alike (the kernel only sees a neighbour table).  Below ~4 k output rows the launch does not fill the chip and
-    # K9b's offset splits win.
     PLANES_MIN_ROWS = switches.PLANES_MIN_ROWS
     emit_planes = True   # plane-form output next to the fp32 one (the consumer is another K9c layer); the U-Net clears it where not
 
-    def _weight_planes(self):
+    _PREPARE = {FP32: "spconv_transpose_weight", SPLIT: "spconv_prepare_weight_split", SPLIT_F16: "spconv_prepare_weight_split_f16",
+                PLANES: "spconv_prepare_weight_planes"}
+
+    def _prepared(self, kernel):
+        """The weights in the form `kernel` reads, made once per value of the parameter (in-place updates and re-assignments re-make
+        them)."""
         w = self.weight
         key = (w._version, w.data_ptr())
-        cache = self.__dict__.get("_wplanes_cache")
-        if cache is None or cache[0] != key:
-            kvol = math.prod(self.kernel_size)
-            cache = (key, hip_ops.spconv_prepare_weight_planes(w.detach().reshape(kvol, self.in_channels, self.out_channels)))
-            self.__dict__["_wplanes_cache"] = cache
-        return cache[1]
+        hit = self._prepared_cache.get(kernel)
+        if hit is None or hit[0] != key:
+            prepare = getattr(hip_ops, self._PREPARE[kernel])
+            hit = self._prepared_cache[kernel] = (key, prepare(w.detach().reshape(-1, self.in_channels, self.out_channels)))
+        return hit[1]
+
+    def kernel_for(self, rows, in_rows, src_widths=None, train=False):
+        """`choose_kernel` for this layer over a table of `rows` rows and `in_rows` input rows."""
+        kind = "subm" if self.subm else "inverse" if self.inverse else "strided"
+        return choose_kernel(kind, self.in_channels, self.out_channels, math.prod(self.kernel_size), rows, in_rows, src_widths, train,
+                             switches.PLANES, switches.TRAIN_PLANES)
+
+    def takes_planes(self, src_widths, rows):
+        """Would this layer read plane sources of these widths on the plane kernel, in inference on `rows` rows?  (What a producer
+        asks before it emits planes instead of fp32 rows.)"""
+        return self.kernel_for(rows, rows, src_widths) == PLANES
 
     def _plane_sources(self, x):
-        """The input in plane form: what the producer emitted, else a conversion of the fp32 features (<= 128 channels per
-        source; a 256-channel input is the concatenation of two halves)."""
+        """The input in plane form: what the producer emitted, else a conversion of the fp32 features."""
         srcs = x.plane_sources
         if srcs is not None and sum(p.c for p in srcs) == self.in_channels and all(p.m == x.indices.size(0) for p in srcs):
             return srcs
-        f = x.features
-        if self.in_channels <= 128:
-            return [hip_ops.to_planes(f)]
-        half = self.in_channels // 2
-        return [hip_ops.to_planes(f[:, :half]), hip_ops.to_planes(f[:, half:])]
-
-    def _use_planes_kernel(self, x, m_out):
-        if not (m_out >= self.PLANES_MIN_ROWS and switches.PLANES):
-            return False
-        cin = self.in_channels
-        cins = [p.c for p in x.plane_sources] if x.plane_sources is not None else ([cin] if cin <= 128 else [cin // 2, cin - cin // 2])
-        return sum(cins) == cin and hip_ops.spconv_planes_supported(cins, self.out_channels, math.prod(self.kernel_size))
+        return _plane_srcs(x.features)
 
     def forward(self, x, scale=None, shift=None, residual=None, relu=False):
         """x: SparseConvTensor.  The optional epilogue arguments are the eval-mode BN affine / residual / ReLU
@@ -328,19 +321,10 @@ class SparseConvolution(SparseModule):
             shift = self.bias
         elif shift is not None and self.bias is not None:
             shift = shift + (self.bias * scale if scale is not None else self.bias)
-        if (not torch.is_grad_enabled() and x.plane_sources is not None and x.indices.size(0) > 0
-                and self._use_planes_kernel(x, nbr.size(0))):  # (reads the plane sources only: a lazy concatenation stays unwritten)
-            out, planes = hip_ops.spconv_forward_planes(self._plane_sources(x), self._weight_planes(), nbr.size(1), self.out_channels,
-                                                        nbr, scale=scale, shift=shift, residual=residual, relu=relu,
-                                                        want_planes=self.emit_planes and self.out_channels <= 128)
-            y = x._like(out, out_indices, out_shape)
-            y.plane_sources = [planes] if planes is not None else None
-            return y
-        feat = x.features
-        needs_grad = torch.is_grad_enabled() and (feat.requires_grad or self.weight.requires_grad)
-        if needs_grad:  # training: the epilogue stays in autograd-visible torch ops
-            out = _SparseConvFn.apply(feat, self.weight, rb, self.inverse, self._use_split_kernel_training(),
-                                      switches.TRAIN_PLANES and switches.PLANES)
+        # (under no_grad `x.features` is not read here: a layer on the plane kernel leaves a lazy concatenation / thunk unformed)
+        if torch.is_grad_enabled() and (x.features.requires_grad or self.weight.requires_grad):
+            # training: the epilogue stays in autograd-visible torch ops
+            out = _SparseConvFn.apply(x.features, self.weight, rb, self.inverse, True, switches.TRAIN_PLANES and switches.PLANES)
             if scale is not None:
                 out = out * scale
             if shift is not None:
@@ -349,26 +333,23 @@ class SparseConvolution(SparseModule):
                 out = out + residual
             if relu:
                 out = torch.relu(out)
-        elif feat.size(0) > 0 and self._use_planes_kernel(x, nbr.size(0)):
-            out, planes = hip_ops.spconv_forward_planes(self._plane_sources(x), self._weight_planes(), nbr.size(1), self.out_channels,
-                                                        nbr, scale=scale, shift=shift, residual=residual, relu=relu,
-                                                        want_planes=self.emit_planes and self.out_channels <= 128)
+            return x._like(out, out_indices, out_shape)
+        kvol, cout, epilogue = nbr.size(1), self.out_channels, dict(scale=scale, shift=shift, residual=residual, relu=relu)
+        kernel = self.kernel_for(nbr.size(0), x.indices.size(0), None if x.plane_sources is None else [p.c for p in x.plane_sources])
+        if kernel == PLANES:
+            out, planes = hip_ops.spconv_forward_planes(self._plane_sources(x), self._prepared(PLANES), kvol, cout, nbr,
+                                                        want_planes=self.emit_planes and cout <= 128, **epilogue)
             y = x._like(out, out_indices, out_shape)
             y.plane_sources = [planes] if planes is not None else None
             return y
-        elif self._use_split_kernel(nbr.size(0)) and feat.size(0) > 0:
-            if (self.in_channels >= 256  # (measured at 256 .. 1024 input channels; below, the conversion is the gain)
-                    and hip_ops.spconv_split_planes_supported(self.in_channels, self.out_channels)
-                    and hip_ops.rows_to_planes_supported(feat)):
-                # K9b-XP: the deep levels (512 / 1024 input channels on a few thousand rows) with both operands as f16 planes
-                out = hip_ops.spconv_forward_split_planes(hip_ops.rows_to_planes(feat), self._weight_split_f16(), nbr.size(1),
-                                                          self.out_channels, nbr, scale=scale, shift=shift, residual=residual, relu=relu)
-            else:
-                out = hip_ops.spconv_forward_split(feat, self._weight_split(), nbr.size(1), self.out_channels, nbr, scale=scale,
-                                                   shift=shift, residual=residual, relu=relu)
+        feat = x.features
+        if kernel == SPLIT_F16 and hip_ops.rows_to_planes_supported(feat):
+            # K9b-XP: the deep levels (512 / 1024 input channels on a few thousand rows) with both operands as f16 planes
+            out = hip_ops.spconv_forward_split_planes(hip_ops.rows_to_planes(feat), self._prepared(SPLIT_F16), kvol, cout, nbr, **epilogue)
+        elif kernel in (SPLIT, SPLIT_F16):
+            out = hip_ops.spconv_forward_split(feat, self._prepared(SPLIT), kvol, cout, nbr, **epilogue)
         else:
-            out = hip_ops.spconv_forward(feat, self._weight_t(), nbr, scale=scale, shift=shift, residual=residual,
-                                         relu=relu)
+            out = hip_ops.spconv_forward(feat, self._prepared(FP32), nbr, **epilogue)
         return x._like(out, out_indices, out_shape)
 
 

@@ -117,7 +117,10 @@ def test_a_write_further_into_the_guard_reports_its_first_byte():
 
 
 # ------------------------------------------------------------------------------------------------ coverage of hip_ops.py
-_ALLOCATES = re.compile(r"torch\.empty|empty_like|torch\.zeros|torch\.full|_lib\.workspace\(|_workspace_bytes|_arena_bytes")
+# `_prepare_weight` is the shared body of the three spconv_prepare_weight_* wrappers, no wrapper itself: each of them allocates by
+# calling it (and counts here for that), and their guard-band cases run it
+_SHARED_BODIES = {"_prepare_weight"}
+_ALLOCATES = re.compile(r"torch\.empty|empty_like|torch\.zeros|torch\.full|_lib\.workspace\(|_workspace_bytes|_arena_bytes|_prepare_weight\(")
 _SCRATCH = re.compile(r"_lib\.workspace\(|_workspace_bytes|_arena_bytes")
 
 
@@ -128,7 +131,7 @@ def allocating_wrappers():
         src = f.read()
     alloc, scratch = set(), set()
     for node in ast.parse(src).body:
-        if isinstance(node, ast.FunctionDef):
+        if isinstance(node, ast.FunctionDef) and node.name not in _SHARED_BODIES:
             body = ast.get_source_segment(src, node)
             if _ALLOCATES.search(body):
                 alloc.add(node.name)

@@ -389,6 +389,62 @@ def test_sparse_unet_on_the_planes_kernel_vs_oracle(fsf_pair, frame1, device, mo
     assert len(calls) >= 20 and ([128, 128], 128) in calls and ([64], 64) in calls and any(c[1] == 256 for c in calls)
 
 
+def test_sparse_unet_layers_run_on_the_kernels_the_decision_names(fsf_pair, frame1, device, monkeypatch):
+    """Every convolution of a U-Net inference, with the default row thresholds and with the plane kernel's lowered to 64: the
+    hip_ops entry each layer calls, with (cin, cout, table rows), is the one `choose_kernel` names for the layer's kind and shape, the
+    rows of its table and input and the plane sources handed to it; the two runs together reach all four entries."""
+    from fullysparsefusion_amd import hip_ops, switches
+    from fullysparsefusion_amd.mmdet3d_plugin.ops import spconv as sp
+
+    model, cpu = fsf_pair
+    pts = torch.from_numpy(frame1["points"][:, :5].copy())
+    ex = omod.segmentor_extract_feat(cpu.segmentor, [pts])
+    entry_of = {sp.PLANES: "spconv_forward_planes", sp.SPLIT_F16: "spconv_forward_split_planes", sp.SPLIT: "spconv_forward_split",
+                sp.FP32: "spconv_forward"}
+    shape_of = {  # entry -> (cin, cout, table rows) of a call's arguments
+        "spconv_forward": lambda feat, weight_t, nbr, **k: (feat.size(1), weight_t.size(1), nbr.size(0)),
+        "spconv_forward_split": lambda feat, planes, kvol, cout, nbr, **k: (feat.size(1), cout, nbr.size(0)),
+        "spconv_forward_split_planes": lambda xp, planes, kvol, cout, nbr, **k: (xp.c, cout, nbr.size(0)),
+        "spconv_forward_planes": lambda sources, wplanes, kvol, cout, nbr, **k: (sum(p.c for p in sources), cout, nbr.size(0)),
+    }
+    called, predicted = [], []
+
+    def spy_on(name):
+        orig = getattr(hip_ops, name)
+
+        def spy(*a, **k):
+            called.append((name, *shape_of[name](*a, **k)))
+            return orig(*a, **k)
+
+        monkeypatch.setattr(hip_ops, name, spy)
+
+    for name in shape_of:
+        spy_on(name)
+    layer_forward = sp.SparseConvolution.forward
+
+    def predicting_forward(self, x, *a, **k):
+        rb = self._rulebook(x)
+        rows = (rb.nbr_inv if self.inverse else rb.nbr).size(0)
+        widths = None if x.plane_sources is None else [p.c for p in x.plane_sources]
+        kind = "subm" if self.subm else "inverse" if self.inverse else "strided"
+        kernel = sp.choose_kernel(kind, self.in_channels, self.out_channels, 27, rows, x.indices.size(0), widths, False, switches.PLANES,
+                                  switches.TRAIN_PLANES)
+        predicted.append((entry_of[kernel], self.in_channels, self.out_channels, rows))
+        return layer_forward(self, x, *a, **k)
+
+    monkeypatch.setattr(sp.SparseConvolution, "forward", predicting_forward)
+    inputs = dict(voxel_feats=ex["voxel_feats"].to(device), voxel_coors=ex["voxel_coors"].to(device), batch_size=1)
+    with torch.no_grad():
+        model.segmentor.backbone(inputs)
+        default_run = len(called)
+        monkeypatch.setattr(sp.SparseConvolution, "PLANES_MIN_ROWS", 64)
+        model.segmentor.backbone(inputs)
+    assert default_run >= 20 and len(called) == 2 * default_run == len(predicted), (default_run, len(called), len(predicted))
+    assert called == predicted, [(c, p) for c, p in zip(called, predicted) if c != p][:4]
+    assert {c[0] for c in called} == set(shape_of), sorted({c[0] for c in called})
+    assert called[:default_run] != called[default_run:]  # (the lowered threshold moved layers onto the plane kernel)
+
+
 @pytest.mark.parametrize("norm,act,c", [(dict(type="LN", eps=1e-3), "gelu", 64), (dict(type="naiveSyncBN1d", eps=1e-3, momentum=0.01), "relu", 64),
                                         (dict(type="LN", eps=1e-3), "gelu", 16)])  # 16 channels: the library product + fsf_gather_rows_add
 def test_grouped_concat_training_equals_the_concat_path(plugin, device, monkeypatch, norm, act, c):

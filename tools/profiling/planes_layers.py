@@ -31,14 +31,13 @@ for i, (m, feat, nbr, kw) in enumerate(calls):
     kvol = math.prod(m.kernel_size); cin, cout = m.in_channels, m.out_channels
     w = m.weight.detach().reshape(kvol, cin, cout)
     pairs = float((nbr >= 0).sum())
-    b = t(lambda: hip_ops.spconv_forward_split(feat, m._weight_split(), kvol, cout, nbr, **kw))
-    cins = [cin] if cin <= 128 else [cin // 2, cin - cin // 2]
-    if hip_ops.spconv_planes_supported(cins, cout, kvol):
+    b = t(lambda: hip_ops.spconv_forward_split(feat, m._prepared(sp.SPLIT), kvol, cout, nbr, **kw))
+    if hip_ops.spconv_planes_supported(sp.source_widths(cin), cout, kvol):
         wpl = hip_ops.spconv_prepare_weight_planes(w)
-        srcs = [hip_ops.to_planes(feat)] if cin <= 128 else [hip_ops.to_planes(feat[:, :cin // 2]), hip_ops.to_planes(feat[:, cin // 2:])]
+        srcs = sp._plane_srcs(feat)
         c = t(lambda: hip_ops.spconv_forward_planes(srcs, wpl, kvol, cout, nbr, want_planes=cout <= 128, **kw))
         tp = t(lambda: hip_ops.to_planes(feat[:, :min(cin, 128)]))
-        ref = hip_ops.spconv_forward_split(feat, m._weight_split(), kvol, cout, nbr, **kw)
+        ref = hip_ops.spconv_forward_split(feat, m._prepared(sp.SPLIT), kvol, cout, nbr, **kw)
         got = hip_ops.spconv_forward_planes(srcs, wpl, kvol, cout, nbr, **kw)[0]
         d = float((ref - got).abs().max()) / max(1.0, float(ref.abs().max()))
         tf = 2 * pairs * cin * cout / c / 1e6
