@@ -1,5 +1,5 @@
 """Per-element error budgets for the kernels that reproduce an fp32 product on the f16 / bf16 matrix cores (K9 / K9b / K9c / K9b-XP
-sparse convolutions, K22 / K22f / K22h Linear layers, the K10p weight gradient): seeded input families whose rows, input columns and
+sparse convolutions, K22 / K22f / K22h Linear layers, the K10 / K10p weight gradient): seeded input families whose rows, input columns and
 output channels differ by 2^12 .. 2^30 in magnitude, the budget each output ELEMENT is held to, numpy emulations of the documented
 operand formats and planted defects of the kinds these kernels have had.  A plain module (no fixtures, nothing collected);
 tests/test_product_budget_cpu.py shows what the budgets stand on, tests/test_product_budget_gpu.py holds the kernels to them.
@@ -37,7 +37,7 @@ LNA_KC = 32                 # K22f: the row scale follows the running maximum ov
 PLANE_CHUNK = 128           # fsf_to_planes: one scale per (row, 128-channel chunk)
 K22F_ADDEND_CAP_EXP = 40    # K22f with a row addend: s_x * s_w <= 2^40
 K9BXP_UNIT_CAP_EXP = 60     # K9b-XP: a row's unit s_row <= 2^60
-BW_RT = 32                  # K10p: pairs per stage; the pair range is split when cap > 8 * BW_RT
+BW_RT = 32                  # K10 / K10p: pairs per stage; the pair range is split when cap > 8 * BW_RT
 WGRAD_SPLIT_N = 8 * BW_RT + 1  # smallest pair count of a dense layer (kvol = 1) with nsplit > 1: 257
 
 # kernel -> (x scale rule, weight scale rule, g, m)
@@ -51,7 +51,8 @@ SCALE_RULES = {
     "K22f": ("row_running", "layer", G_F16, 2.0),
     "K22f-grouped": ("row_running", "layer", G_F16, 3.0),
     "K22h": ("row", "layer", G_F16, 8.0),
-    "K10p": ("fp32", "fp32", 0.0, 2.0),         # fp32 matrix pipe; its test grants no factor: 2
+    "K10": ("fp32", "fp32", 0.0, 2.0),          # fp32 matrix pipe (cin <= 64 or cout <= 64); no test grants it a factor: 2
+    "K10p": ("bf16x3", "bf16x3", 0.0, 2.0),     # bf16 matrix cores (cin > 64 and cout > 64): the six terms of K9b / K22, their factor
 }
 
 
@@ -268,7 +269,7 @@ class Budget:
     def __init__(self, prod, kernel, x_rule=None, eps_x_rows=None):
         xr, wr, self.g, self.m = SCALE_RULES[kernel]
         xr = x_rule or xr
-        self.kernel = kernel
+        self.kernel, self.prod = kernel, prod
         self.want = prod.want()
         self.A = np.abs(prod.X) @ np.abs(prod.w)
         if prod.addend is not None:
@@ -326,11 +327,17 @@ def emulate_f16(prod, x_rule="row", defect=None):
     return y if prod.addend is None else y + prod.addend.astype(np.float64)
 
 
-def emulate_bf16(prod, parts=3):
-    """The bf16 split in float64: the six leading cross terms of the exact 3-way split, or every term of a 2-way split (planted)."""
+BF16_TERMS = ((0, 0), (0, 1), (1, 0), (0, 2), (2, 0), (1, 1))  # (piece of X, piece of W): 0 = hi, 1 = mid, 2 = lo
+
+
+def emulate_bf16(prod, parts=3, drop=None):
+    """The bf16 split in float64: the six leading cross terms of the exact 3-way split, or every term of a 2-way split (planted).
+    `drop=(i, j)`: the planted defect of one cross term left out."""
     xs = [prod.rows(p) for p in split_bf16(prod.x, parts)]
     ws = split_bf16(prod.w, parts)
-    terms = [(0, 0), (0, 1), (1, 0), (0, 2), (2, 0), (1, 1)] if parts == 3 else [(0, 0), (0, 1), (1, 0), (1, 1)]
+    terms = list(BF16_TERMS) if parts == 3 else [(0, 0), (0, 1), (1, 0), (1, 1)]
+    if drop is not None:
+        terms.remove(tuple(drop))
     y = sum(xs[i] @ ws[j] for i, j in terms)
     return y if prod.addend is None else y + prod.addend.astype(np.float64)
 
@@ -403,37 +410,62 @@ def wgrad_pair_capacity(table):
     return int(table[6:]) if table.startswith("dense-") else conv_tables()[table][0].shape[0]
 
 
-def wgrad_nsplit(cap, cin, cout, kvol):
-    """bwd_plan of csrc/spconv_bwd.hip: into how many ranges K10p splits an offset's pair list."""
+def wgrad_plan(cap, cin, cout, kvol):
+    """bwd_plan of csrc/spconv_bwd.hip (its lines are pinned by tests/test_product_budget_cpu.py): (ta, tb, tiles_a, tiles_b, nsplit,
+    range) — the channel tile, the channel tiles per side, into how many ranges an offset's pair list is split, pairs per range."""
     cdiv = lambda a, b: -(-a // b)
-    tiles = cdiv(cin, 64 if cin <= 64 else 128) * cdiv(cout, 64 if cout <= 64 else 128)
+    ta, tb = 64 if cin <= 64 else 128, 64 if cout <= 64 else 128
+    tiles = cdiv(cin, ta) * cdiv(cout, tb)
     s = max(1, min(cdiv(6144 if kvol >= 8 else 512, kvol * tiles), cdiv(cap, 8 * BW_RT)))
     r = max(BW_RT, cdiv(cdiv(cap, s), BW_RT) * BW_RT)
-    return cdiv(max(cap, 1), r)
+    return ta, tb, cdiv(cin, ta), cdiv(cout, tb), cdiv(max(cap, 1), r), r
+
+
+def wgrad_nsplit(cap, cin, cout, kvol):
+    """Into how many ranges the weight gradient splits an offset's pair list."""
+    return wgrad_plan(cap, cin, cout, kvol)[4]
+
+
+def wgrad_kernel(cin, cout):
+    """Which kernel fsf_spconv_backward_weight launches: `if (cap > 0 && ta == 128 && tb == 128)` is the bf16 one."""
+    ta, tb = wgrad_plan(1, cin, cout, 1)[:2]
+    return "K10p" if ta == 128 and tb == 128 else "K10"
 
 
 @functools.lru_cache(maxsize=None)
-def wgrad_case(table):
+def wgrad_case(table, cin=WGRAD_CIN, cout=WGRAD_COUT, absolute=False):
     """spconv_backward_weight on a table of the sparse family; 'dense-<n>': linear_backward_weight (identity pairs) on n rows — 192 = the
-    family's rows, WGRAD_SPLIT_N = the first pair count at which K10p splits the pair range of a dense layer.  Which cases split is
-    `wgrad_nsplit(wgrad_pair_capacity(table), ...)`, asserted in tests/test_product_budget_cpu.py."""
+    family's rows, WGRAD_SPLIT_N = the first pair count at which the pair range of a dense layer is split.  Which cases split is
+    `wgrad_nsplit(wgrad_pair_capacity(table), ...)`, asserted in tests/test_product_budget_cpu.py.  The channel counts pick the kernel
+    (`wgrad_kernel`) and with it the budget's rule.  `absolute`: both operands replaced by their absolute values — the truncating split
+    keeps the sign, so every piece is then non-negative and whatever a dropped cross term leaves out adds up coherently."""
     if table.startswith("dense-"):
         n = int(table[6:])
         cls = sparse_sites()[2] if n == sparse_sites()[0].shape[0] else dense_rows_classes(n)
-        feat, gout = wgrad_family(n, n, WGRAD_CIN, WGRAD_COUT, cls)
+        feat, gout = wgrad_family(n, n, cin, cout, cls)
         nbr = np.arange(n, dtype=np.int32)[:, None]
     else:
         nbr, m_in = conv_tables()[table]
         cls = sparse_sites()[2] if table != "inverse" else np.arange(m_in) % 3
-        feat, gout = wgrad_family(m_in, nbr.shape[0], WGRAD_CIN, WGRAD_COUT, cls)
+        feat, gout = wgrad_family(m_in, nbr.shape[0], cin, cout, cls)
+    if absolute:
+        feat, gout = np.abs(feat), np.abs(gout)
+    kernel = wgrad_kernel(cin, cout)
     parts = []
     for k in range(nbr.shape[1]):
         out_rows = np.nonzero(nbr[:, k] >= 0)[0]
-        parts.append(Budget(wgrad_product(feat, gout, nbr[out_rows, k].astype(np.int64), out_rows), "K10p"))
-    return dict(kernel="K10p", feat=feat, gout=gout, cls=cls, nbr=nbr, parts=parts, budget=StackedBudget(parts))
+        parts.append(Budget(wgrad_product(feat, gout, nbr[out_rows, k].astype(np.int64), out_rows), kernel))
+    return dict(kernel=kernel, cin=cin, cout=cout, feat=feat, gout=gout, cls=cls, nbr=nbr, parts=parts, budget=StackedBudget(parts))
 
 
 WGRAD_TABLES = ("subm", "strided", "inverse", "dense-192", "dense-%d" % WGRAD_SPLIT_N)
+K10P_SHAPES = ((68, 68), (132, 68))  # one partial 128 x 128 tile; two `a` tiles
+K10P_CASES = tuple((t, cin, cout, ab) for ab in (False, True) for cin, cout in K10P_SHAPES for t in WGRAD_TABLES)
+
+
+def wgrad_emulate_bf16(c, drop=None):
+    """The stacked [kvol * cin, cout] result of the six-term bf16 arithmetic on a `wgrad_case`, with one cross term left out (`drop`)."""
+    return np.concatenate([emulate_bf16(p.prod, 3, drop) for p in c["parts"]], 0)
 
 
 def class_name(c):

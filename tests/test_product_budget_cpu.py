@@ -90,10 +90,11 @@ def test_two_way_bf16_split_leaves_the_budget(family, name, arg):
 
 @pytest.mark.parametrize("table", P.WGRAD_TABLES)
 def test_weight_gradient_budget(table):
-    """fp32 operands: torch's fp32 product is inside the budget (m = 2 over its own worst ratio), a 2-way bf16 split of the operands is
+    """K10 (32 x 68 channels: the fp32 matrix pipe), fp32 operands: torch's fp32 product is inside the budget (m = 2 over its own worst ratio), a 2-way bf16 split of the operands is
     outside; offsets without a pair ask for exact zeros."""
     c = P.wgrad_case(table)
     b = c["budget"]
+    assert c["kernel"] == b.kernel == "K10" and P.SCALE_RULES["K10"][:2] == ("fp32", "fp32")
     assert float((b.err32[b.A > 0] / b.B[b.A > 0]).max()) <= 1.0
     assert not b.err32[b.A == 0].any() and not b.want[b.A == 0].any()
     assert b.floor_share() == 0.0
@@ -114,6 +115,27 @@ def test_weight_gradient_budget(table):
         assert c["feat"].shape[0] == 8 * P.BW_RT + 1
 
 
+@pytest.mark.parametrize("table,cin,cout,absolute", P.K10P_CASES)
+def test_k10p_budget_holds_the_six_terms_and_no_five(table, cin, cout, absolute):
+    """K10p (cin > 64 and cout > 64: the bf16 matrix cores) on 68 x 68 (one partial tile) and 132 x 68 (two `a` tiles), signed and with
+    both operands made non-negative: the six-term arithmetic and torch's fp32 product stay inside the budget; with any ONE cross term
+    other than hi * hi left out the result leaves it, on every case.  Measured here, max err / B over the 20 cases: six terms 0.06 ..
+    0.50; without hi * lo, lo * hi or mid * mid 9.0 .. 74; without hi * mid or mid * hi 2 900 .. 11 700 — so a factor m up to 8 instead
+    of 2 would still tell every five-term kernel from the six-term one."""
+    c = P.wgrad_case(table, cin, cout, absolute)
+    b = c["budget"]
+    assert c["kernel"] == b.kernel == "K10p" and P.wgrad_plan(P.wgrad_pair_capacity(table), cin, cout, c["nbr"].shape[1])[:2] == (128, 128)
+    assert (b.g, b.m) == (0.0, 2.0) and b.floor_share() == 0.0 and not b.floor.any()
+    assert absolute == bool((c["feat"] >= 0).all() and (c["gout"] >= 0).all())
+    ratio, at = b.worst(P.wgrad_emulate_bf16(c))
+    assert ratio <= 1.0, (ratio, at)
+    assert float((b.err32[b.A > 0] / b.B[b.A > 0]).max()) <= 1.0
+    assert not b.err32[b.A == 0].any() and not b.want[b.A == 0].any()
+    for drop in P.BF16_TERMS[1:]:
+        ratio, at = b.worst(P.wgrad_emulate_bf16(c, drop))
+        assert ratio > 1.0, (drop, ratio, at)
+
+
 def test_floor_dominated_share_per_format_exceeds_a_quarter_for_the_f16_forms():
     """Where the format's floor, not the arithmetic, sets the budget: the share of elements with floor > (g + m 2^-23) A, per (family,
     format), never averaged over formats.
@@ -128,7 +150,7 @@ def test_floor_dominated_share_per_format_exceeds_a_quarter_for_the_f16_forms():
     plain channel of every row, 2^-12 rows included, is held to the arithmetic bound, and the planted defects are > 10 x over there
     (test_shared_scale_and_dropped_lo_plane_leave_the_budget); and on the floor-dominated channels the budget is still per element and
     still 15 (2^-10 channels) or 5 (2^-20 channels) bits below the element's own size.
-    The exact formats (bf16 x 3: K9b, K22; fp32 operands: K9, K10p) have no floor: share 0."""
+    The exact formats (bf16 x 3: K9b, K22, K10p; fp32 operands: K9, K10) have no floor: share 0."""
     for c in ALL:
         b = _case(*c)["budget"]
         width = b.A.shape[1]
@@ -238,18 +260,36 @@ def test_scale_rules_and_caps_equal_the_kernel_sources():
     # the caps
     assert "- 127 + %d;" % P.K22F_ADDEND_CAP_EXP in lna and "s * s_w stays <= 2^%d" % P.K22F_ADDEND_CAP_EXP in lna
     assert "sc_x[rg] = fmaxf(raw, 0x1p-%df);" % P.K9BXP_UNIT_CAP_EXP in split
-    # K10p: fp32 operands on the fp32 matrix pipe; the pair range splits from 8 stages + 1 pair
-    assert "v_mfma_f32_16x16x4_f32" in bwd and "f16" not in bwd.lower().replace("bf16", "")
+    # K10: fp32 operands on the fp32 matrix pipe.  K10p: the exact 3-way bf16 split (truncation, the remainder formed in fp32) and the
+    # six cross terms of P.BF16_TERMS on the bf16 matrix cores.  Neither has an f16 form.  Which shapes run which: both tiles 128 wide.
+    k10, k10p = bwd[:bwd.index("// K10p (round 4)")], bwd[bwd.index("// K10p (round 4)"):]
+    assert "v_mfma_f32_16x16x4_f32" in k10 and "__builtin_amdgcn_mfma_f32_16x16x4f32(" in k10 and "bf16" not in k10
+    assert "v_mfma_f32_16x16x32_bf16" in k10p and k10p.count("__builtin_amdgcn_mfma_f32_16x16x32_bf16(af[ta][TERM_A[term]], bf[TERM_B[term]]") == 1
+    assert "f16" not in bwd.lower().replace("bf16", "")
+    term_a, term_b = (tuple(int(v) for v in re.search(r"constexpr int TERM_%s\[6\] = \{([0-9, ]+)\};" % ab, k10p).group(1).split(","))
+                      for ab in "AB")
+    assert sorted(zip(term_a, term_b)) == sorted(P.BF16_TERMS)
+    assert k10p.count("& 0xffff0000u") == 4 and "const float ar = __fsub_rn(a, ah), br = __fsub_rn(b, bh);" in k10p
+    assert "  if (cap > 0 && ta == 128 && tb == 128) {\n" in bwd and bwd.count("spconv_bwd_weight_split_kernel, grid, dim3(256), BWS_SMEM") == 1
+    assert (P.wgrad_kernel(64, 68), P.wgrad_kernel(68, 64), P.wgrad_kernel(68, 68), P.wgrad_kernel(P.WGRAD_CIN, P.WGRAD_COUT)) == ("K10", "K10", "K10p", "K10")
+    # the pair range splits from 8 stages + 1 pair
     assert int(re.search(r"constexpr int BW_RT = (\d+);", bwd).group(1)) == P.BW_RT
     for line in ("*ta = cin <= 64 ? 64 : 128;", "*tb = cout <= 64 ? 64 : 128;", "int64_t s = fsf_cdiv(kvol >= 8 ? 6144 : 512, kvol * tiles);",
                  "const int64_t max_s = fsf_cdiv(cap, 8 * BW_RT);", "int64_t r = fsf_align_up(fsf_cdiv(cap, s), BW_RT);",
                  "*nsplit = fsf_cdiv(cap > 0 ? cap : 1, r);"):
-        assert line in bwd, line  # P.wgrad_nsplit mirrors these
+        assert line in bwd, line  # P.wgrad_plan mirrors these
+    for line in ("*range = (int)r;", "if (r < BW_RT) r = BW_RT;", "if (s > max_s) s = max_s;", "if (s < 1) s = 1;",
+                 "const int64_t tiles = (int64_t)fsf_cdiv(cin, *ta) * fsf_cdiv(cout, *tb);"):
+        assert line in bwd, line
     assert "cap = max(m_out, 1)" in open(os.path.join(ROOT, "fullysparsefusion_amd", "hip_ops.py")).read()  # rulebook_to_pairs
 
 
 def test_weight_gradient_cases_on_both_sides_of_the_range_split():
-    """Which weight-gradient cases make K10p split an offset's pair range (nsplit > 1, partial sums folded by the second kernel)."""
+    """Which weight-gradient cases split an offset's pair range (nsplit > 1, partial sums folded by the second kernel): the same for
+    the K10 shape and the two K10p shapes."""
+    for cin, cout in ((P.WGRAD_CIN, P.WGRAD_COUT),) + P.K10P_SHAPES:
+        assert {t: P.wgrad_nsplit(P.wgrad_pair_capacity(t), cin, cout, 1 if t.startswith("dense-") else 27) for t in P.WGRAD_TABLES} == {
+            "subm": 1, "strided": 2, "inverse": 1, "dense-192": 1, "dense-257": 2}
     nsplit = {t: P.wgrad_nsplit(P.wgrad_pair_capacity(t), P.WGRAD_CIN, P.WGRAD_COUT, 1 if t.startswith("dense-") else 27) for t in P.WGRAD_TABLES}
     assert {t: P.wgrad_pair_capacity(t) for t in P.WGRAD_TABLES} == {"subm": 192, "strided": 276, "inverse": 192, "dense-192": 192, "dense-257": 257}
     assert nsplit == {"subm": 1, "strided": 2, "inverse": 1, "dense-192": 1, "dense-257": 2}
@@ -276,3 +316,4 @@ def test_factors_over_fp32_equal_the_existing_tests():
     for test, k in (("test_spconv_forward_split_planes_f16x3_vs_float64", "K9b-XP"), ("test_spconv_forward_subm_vs_oracle", "K9"),
                     ("test_spconv_backward_weight_on_strided_and_inverse_tables_equals_float64", "K10p")):
         assert "err32" not in body(test) and P.SCALE_RULES[k][3] == 2.0
+    assert P.SCALE_RULES["K10"][3] == 2.0  # (no test in tests/test_hip_ops.py grants the fp32-pipe weight gradient a factor either)

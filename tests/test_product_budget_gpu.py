@@ -142,13 +142,9 @@ def test_linear_within_budget(ops, device, name, n):
     assert torch.equal(out2, run(**e))
 
 
-@pytest.mark.parametrize("table", P.WGRAD_TABLES)
-def test_weight_gradient_within_budget(ops, device, table):
-    """K10p through spconv_backward_weight (the three tables) and through linear_backward_weight (192 and 257 rows).  The pair range of
-    an offset is split in two (partial sums folded by a second kernel) on the strided table, whose pair lists have room for 276 pairs,
-    and on the 257 rows; tests/test_product_budget_cpu.py derives that from the launch plan, the capacity is asserted here."""
-    c = P.wgrad_case(table)
-    b = c["budget"]
+def _weight_gradient(ops, device, c, table):
+    """The case's weight gradient, twice (the second for the determinism check): through spconv_backward_weight on the device rulebook's
+    pair lists, or through linear_backward_weight ('dense-<n>')."""
     feat, gout = torch.from_numpy(c["feat"]).to(device), torch.from_numpy(c["gout"]).to(device)
     if table.startswith("dense-"):
         run = lambda: ops.linear_backward_weight(feat, gout)
@@ -157,8 +153,32 @@ def test_weight_gradient_within_budget(ops, device, table):
         assert num.cpu().tolist() == [int((c["nbr"][:, k] >= 0).sum()) for k in range(27)]
         assert pairs.shape == (27, 2, P.wgrad_pair_capacity(table))
         run = lambda: ops.spconv_backward_weight(feat, gout, pairs, num)
-    got = run()
+    cin = c["cin"]
     classes = lambda at: "offset %d, input column %s, grad-out column %s" % (
-        at[0] // P.WGRAD_CIN, "2^-12" if at[0] % P.WGRAD_CIN % 4 == 0 else "1", "2^-12" if at[1] % 5 == 0 else "1")
-    _hold("K10p-%s" % table, b, got, classes)
-    assert torch.equal(got, run())
+        at[0] // cin, "2^-12" if at[0] % cin % 4 == 0 else "1", "2^-12" if at[1] % 5 == 0 else "1")
+    return run(), run(), classes
+
+
+@pytest.mark.parametrize("table", P.WGRAD_TABLES)
+def test_weight_gradient_within_budget(ops, device, table):
+    """K10 (32 x 68 channels: the 64 x 128 tile of the fp32 matrix pipe) through spconv_backward_weight (the three tables) and through
+    linear_backward_weight (192 and 257 rows).  The pair range of an offset is split in two (partial sums folded by a second kernel) on
+    the strided table, whose pair lists have room for 276 pairs, and on the 257 rows; tests/test_product_budget_cpu.py derives that from
+    the launch plan, the capacity is asserted here."""
+    c = P.wgrad_case(table)
+    assert c["kernel"] == "K10"
+    got, again, classes = _weight_gradient(ops, device, c, table)
+    _hold("K10-%s" % table, c["budget"], got, classes)
+    assert torch.equal(got, again)
+
+
+@pytest.mark.parametrize("table,cin,cout,absolute", P.K10P_CASES)
+def test_k10p_weight_gradient_within_budget(ops, device, table, cin, cout, absolute):
+    """K10p (both channel counts above 64: the six-term bf16 kernel) on 68 x 68 and 132 x 68 channels, the same five pair layouts, signed
+    and with both operands non-negative (every piece of the truncating split is then non-negative: a dropped term cannot cancel).
+    tests/test_product_budget_cpu.py: the six terms stay below 0.5 of this budget, any five are 9 or more times over it."""
+    c = P.wgrad_case(table, cin, cout, absolute)
+    assert c["kernel"] == "K10p"
+    got, again, classes = _weight_gradient(ops, device, c, table)
+    _hold("K10p-%s-%dx%d%s" % (table, cin, cout, "-abs" if absolute else ""), c["budget"], got, classes)
+    assert torch.equal(got, again)
