@@ -514,7 +514,9 @@ class DevicePointAssembler:
     host->device copy, and `fsf_assemble_sweeps` (K0) does what LoadPointsFromMultiSweeps
     (datasets/pipelines/loading.py:825-877), SaveNoAugPoints (:341-354), PointsRangeFilter and NormalizePoints (:537-563) do
     in numpy / torch on the host — same rows, same order, bit-identical values (tests pin it to input_pipeline.npz through
-    the host classes above).  Returns f32 [N, load_dim + 3] on `device`: what `FSF.simple_test` takes as `points[0]`."""
+    the host classes above).  Returns f32 [N, load_dim + 3] on `device`: what `FSF.simple_test` takes as `points[0]`.
+    When the output feeds `train_augment.DeviceTrainAugment` (K40) construct it with `point_cloud_range=None`: there, too, the range
+    test belongs on the augmented xyz."""
 
     def __init__(self, load_dim=5, sweeps_num=9, pad_empty_sweeps=True, remove_close=True, test_mode=False,
                  point_cloud_range=None, norm_dims=(3,), norm_mean=(0,), norm_std=(255,), close_radius=1.0, augmentations=None):

@@ -442,6 +442,56 @@ int fsf_aug_boxes_map_back(const float* boxes, int64_t box_stride, int32_t box_d
                            float* boxes_out, float* boxes_nms, float* scores_t, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * K40  train-time augmentation of the uploaded cloud and the GT boxes (docs/kernels/K40_train_augment.md)
+ * Replaces the host passes both train pipelines run after SaveNoAugPoints (configs/_base_/datasets/nuscenes_dataloader.py:53-95,
+ *   AV2_dataloader.py:73-105): RandomFlip3D(sync_2d=False) [UNVENDORED mmdet3d.datasets.pipelines.RandomFlip3D], GlobalRotScaleTrans /
+ *   MyGlobalRotScaleTrans with drawn factors (projects/mmdet3d_plugin/datasets/pipelines/transforms_3d.py:59-170), PointsRangeFilter,
+ *   PointShuffle [UNVENDORED mmdet3d.datasets.pipelines.PointShuffle] and MyObjectRangeFilter
+ *   (projects/mmdet3d_plugin/datasets/pipelines/loading.py:367-408) with the box methods it calls [UNVENDORED
+ *   LiDARInstance3DBoxes.flip / rotate / scale / translate / in_range_bev / limit_yaw].  The draws stay on the host
+ *   (mmdet3d_plugin/datasets/train_augment.py::draw_train_augmentation: np.random in the reference's order).
+ *   desc      f32 [FSF_TRAIN_AUGMENT_DESC_WORDS] HOST per frame: (cos, sin, scale, angle, rotate, flip_h, flip_v, tx, ty, tz) — K33's
+ *             seven (cos / sin of the fp32 angle as the host computes them, rotate = 0 for an angle of exactly zero) and the
+ *             translation, each component rounded to fp32; scale > 0
+ * K40a/b fsf_train_augment_points, ONE frame per call:
+ *   points    f32 [n_rows, cols] device (3 <= cols <= 64; columns 0..2 = xyz, the rest — features and SaveNoAugPoints' xyz copy — are
+ *             copied unchanged); n_rows < 2^31
+ *   pc_range  f32 [6] HOST or NULL: the strict in-range test on the AUGMENTED xyz (a NaN coordinate drops the row)
+ *   shuffle_seed >= 0: the survivors in ascending order of key(row) = mix31(row, seed), ties in source order (the key mix:
+ *             docs/kernels/K40_train_augment.md; a deterministic stand-in for PointShuffle's torch.randperm, whose stream cannot be
+ *             reproduced); < 0: no shuffle, the survivors in source order
+ *   out       f32 [n_rows, cols] (capacity): rows [0, count) are written
+ *   count     i64 [1] device (and on the host too when count_host != NULL: one stream sync)
+ * Per row: y -> -y (horizontal), x -> -x (vertical), x' = x c - y s, y' = x s + y c (two rounded products and one rounded sum each, no
+ * FMA), xyz times scale, xyz plus (tx, ty, tz), the range test.  Launches: K40a (keys + count), the radix sort's histogram and one
+ * pass per 8 key bits (4 with the shuffle, 1 without), K40b (gather; re-transforms the row it reads).  Bit-identical to
+ * train_augment.py::augment_points_host.
+ * K40c fsf_train_augment_boxes, one launch for a batch, no workspace, never synchronises:
+ *   boxes / no_aug_boxes  f32 [g, box_dim] device with row strides box_stride / no_aug_stride (box_dim 7..16: x y z_bottom w l h yaw
+ *             [vx vy ...]); labels / no_aug_labels i64 [g]; g = sample_offsets[num_samples] (0 is legal: nothing is launched)
+ *   sample_offsets  i64 [num_samples + 1] HOST: sample k's boxes are rows sample_offsets[k] .. sample_offsets[k + 1]
+ *   desc      f32 [num_samples, FSF_TRAIN_AUGMENT_DESC_WORDS] HOST; 1 <= num_samples <= FSF_TRAIN_AUGMENT_MAX_BATCH
+ *   pc_range  f32 [6] HOST: a box stays when its augmented (x, y) is strictly inside pc_range[[0, 1, 3, 4]]
+ *   boxes_out f32 [g, box_dim]: H flip (y, vy negated, yaw -> -yaw + pi), V flip (x, vx negated, yaw -> -yaw), (x, y) and (vx, vy)
+ *             rotated as the points and yaw -> yaw + angle (the frame of the containment test every GT
+ *             consumer applies, K35a / K36a / K37 / K38: the footprint turns counter-clockwise with yaw), every column but yaw times scale, xyz plus t, yaw -> limit_yaw(0.5, 2 pi) =
+ *             yaw - floor(yaw / fp32(2 pi) + 0.5) * fp32(2 pi); no_aug_boxes_out f32 [g, box_dim]: the input with yaw wrapped
+ *   labels_out / no_aug_labels_out  i64 [g]: the input label, -1 on a dropped row (every consumer of FSF.forward_train skips label < 0);
+ *             an input label < 0 stays as it is
+ * Bit-identical to train_augment.py::augment_boxes_host.
+ */
+#define FSF_TRAIN_AUGMENT_DESC_WORDS 10
+#define FSF_TRAIN_AUGMENT_MAX_BATCH 32
+int64_t fsf_train_augment_points_workspace_bytes(int64_t n_rows);
+int fsf_train_augment_points(const float* points, int64_t n_rows, int32_t cols, const float* desc, const float* pc_range,
+                             int64_t shuffle_seed, float* out, int64_t* count_dev, int64_t* count_host, void* workspace,
+                             int64_t workspace_bytes, void* stream);
+int fsf_train_augment_boxes(const float* boxes, int64_t box_stride, int32_t box_dim, const int64_t* labels, const float* no_aug_boxes,
+                            int64_t no_aug_stride, const int64_t* no_aug_labels, const int64_t* sample_offsets, int32_t num_samples,
+                            const float* desc, const float* pc_range, float* boxes_out, int64_t* labels_out, float* no_aug_boxes_out,
+                            int64_t* no_aug_labels_out, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * K34  camera instance-id planes painted from 2-D detections (docs/kernels/K34_mask_paint.md)
  * Replaces the offline round trip tools/mask_tools/save_mask_nusc.py / save_mask_argo2.py (paint_obj, paint_obj_bbox_only,
  *   get_instance_mask: PNG planes + anno.json) -> LoadMaskFromFiles (projects/mmdet3d_plugin/datasets/pipelines/loading.py:22-339).
