@@ -353,6 +353,11 @@ static int make_geom(ConvGeom* g, int32_t batch_size, const int32_t shape[3], co
   if (g->B < 1 || g->Z < 1 || g->Y < 1 || g->X < 1 || g->kvol < 1 || g->sz < 1 || g->sy < 1 || g->sx < 1 ||
       g->dz < 1 || g->dy < 1 || g->dx < 1 || g->pz < 0 || g->py < 0 || g->px < 0)
     return FSF_ERR_INVALID_ARG;
+  // (a kernel extent larger than the padded input: O = floor(negative / stride) + 1 < 1, which C's division towards zero hides
+  // for a numerator in (-stride, 0))
+  if (g->Z + 2 * g->pz - g->dz * (g->kz - 1) - 1 < 0 || g->Y + 2 * g->py - g->dy * (g->ky - 1) - 1 < 0 ||
+      g->X + 2 * g->px - g->dx * (g->kx - 1) - 1 < 0)
+    return FSF_ERR_INVALID_ARG;
   g->OZ = (g->Z + 2 * g->pz - g->dz * (g->kz - 1) - 1) / g->sz + 1;
   g->OY = (g->Y + 2 * g->py - g->dy * (g->ky - 1) - 1) / g->sy + 1;
   g->OX = (g->X + 2 * g->px - g->dx * (g->kx - 1) - 1) / g->sx + 1;
@@ -453,7 +458,10 @@ extern "C" int fsf_rulebook_strided(const int32_t* indices, int64_t m, int32_t b
     FSF_HIP_TRY(hipMemcpyAsync(m_out_dev, &tmp, sizeof(int64_t), hipMemcpyHostToDevice, stream));
     FSF_STREAM_WAIT(stream);
   }
-  if (m_out == 0) return FSF_OK;
+  if (m_out == 0) {  // no input proposes an output site: no forward rows, and every entry of the inverse table is "no output row"
+    if (nbr_inv) FSF_HIP_TRY(hipMemsetAsync(nbr_inv, 0xFF, (size_t)cand * sizeof(int32_t), stream));
+    return FSF_OK;
+  }
   // ascending linear (b,z,y,x) order of the output sites
   hipLaunchKernelGGL(rb_iota_kernel, dim3(fsf_stream_grid(m_out, 256)), dim3(256), 0, stream, lv_a, m_out);
   const uint64_t total_cells = (uint64_t)g.B * g.OZ * g.OY * g.OX;

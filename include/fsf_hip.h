@@ -823,6 +823,8 @@ int fsf_rulebook_subm(const int32_t* indices, int64_t m, int32_t batch_size, con
  *   out_indices i32 [cap,4]; nbr i32 [cap,kvol]; m_out_dev/m_out_host as in fsf_unique_rows.
  * Also emits the transposed table for SparseInverseConv3d on the same indice_key:
  *   nbr_inv i32 [m, kvol] (fine row -> coarse row per offset) or NULL.
+ * No input may reach an output site (m > 0, m_out = 0: every site above the last output's extent at padding 0): nbr_inv is
+ * then all -1, nothing else is written.  out_shape < 1 in an axis (kernel extent beyond the padded input): FSF_ERR_INVALID_ARG.
  */
 int fsf_rulebook_strided(const int32_t* indices, int64_t m, int32_t batch_size, const int32_t spatial_shape[3],
                          const int32_t ksize[3], const int32_t stride[3], const int32_t padding[3],
