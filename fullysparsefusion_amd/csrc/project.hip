@@ -2,6 +2,7 @@
 // lookup.  See include/fsf_hip.h.  One thread per (point, camera); the mask is read in its stored integer
 // type (no float copy).  Every fp32 operation is an explicit round-to-nearest op in the order the
 // reference's elementwise PyTorch ops apply them (FSF.py:169-200), so pixel indices are bit-exact.
+#include "bilinear_taps.h"  // proj_row, and K13b's tap arithmetic (shared with K13c, project_bwd.hip)
 #include "common.h"
 #include "radix_sort.h"
 #include "scan.h"
@@ -18,16 +19,6 @@ struct ProjArgs {
   int stride;
   int ncam, ncls, H, W;
 };
-
-// pts_4d @ lidar2img^T for one output row: ((x*m0 + y*m1) + z*m2) + m3 as an fma chain in k order,
-// which is what the CPU sgemm micro-kernel of the in-container reference evaluates (see oracle/project.py).
-__device__ __forceinline__ float proj_row(const float* m, float x, float y, float z) {
-  float acc = __fmul_rn(x, m[0]);
-  acc = __fmaf_rn(y, m[1], acc);
-  acc = __fmaf_rn(z, m[2], acc);
-  acc = __fmaf_rn(1.0f, m[3], acc);
-  return acc;
-}
 
 template <typename MaskT>
 __global__ void __launch_bounds__(256) project_gather_kernel(ProjArgs a) {
@@ -303,26 +294,10 @@ __global__ void __launch_bounds__(256) project_bilinear_kernel(BilinArgs a) {
     const float x = p[0], y = p[1], z = p[2];
     int seen = 0;
     for (int cam = 0; cam < a.ncam; ++cam) {
-      const float* m = s_mat + cam * 12;
-      float px = proj_row(m, x, y, z), py = proj_row(m + 4, x, y, z), pz = proj_row(m + 8, x, y, z);
-      const bool depth_valid = pz > 1e-3f;
-      pz = fminf(fmaxf(pz, 1e-5f), 1e5f);
-      px = __fdiv_rn(__fdiv_rn(px, pz), fw);
-      py = __fdiv_rn(__fdiv_rn(py, pz), fh);
-      const float gx = __fmul_rn(__fsub_rn(px, 0.5f), 2.0f), gy = __fmul_rn(__fsub_rn(py, 0.5f), 2.0f);
-      const bool valid = depth_valid && gx > -1.0f && gx < 1.0f && gy > -1.0f && gy < 1.0f;
-      seen += valid ? 1 : 0;
-      // grid_sample, align_corners = False
-      const float ix = ((gx + 1.0f) * (float)a.Wf - 1.0f) * 0.5f, iy = ((gy + 1.0f) * (float)a.Hf - 1.0f) * 0.5f;
-      const float x0f = floorf(ix), y0f = floorf(iy);
-      const float wx1 = ix - x0f, wy1 = iy - y0f, wx0 = 1.0f - wx1, wy0 = 1.0f - wy1;
-      const int x0 = (int)x0f, y0 = (int)y0f;
-      const bool inx0 = x0 >= 0 && x0 < a.Wf, inx1 = x0 + 1 >= 0 && x0 + 1 < a.Wf;
-      const bool iny0 = y0 >= 0 && y0 < a.Hf, iny1 = y0 + 1 >= 0 && y0 + 1 < a.Hf;
-      const float w00 = valid && inx0 && iny0 ? wx0 * wy0 : 0.0f, w01 = valid && inx1 && iny0 ? wx1 * wy0 : 0.0f;
-      const float w10 = valid && inx0 && iny1 ? wx0 * wy1 : 0.0f, w11 = valid && inx1 && iny1 ? wx1 * wy1 : 0.0f;
-      const int xa = min(max(x0, 0), a.Wf - 1), xb = min(max(x0 + 1, 0), a.Wf - 1);
-      const int ya = min(max(y0, 0), a.Hf - 1), yb = min(max(y0 + 1, 0), a.Hf - 1);
+      const BilinearTaps tp = bilinear_taps(s_mat + cam * 12, x, y, z, fw, fh, a.Hf, a.Wf);  // (bilinear_taps.h)
+      seen += tp.valid ? 1 : 0;
+      const float w00 = tp.w00, w01 = tp.w01, w10 = tp.w10, w11 = tp.w11;
+      const int xa = tp.xa, xb = tp.xb, ya = tp.ya, yb = tp.yb;
       float* o = a.reduce ? a.out + i * a.C : a.out + (i * a.ncam + cam) * a.C;
       const bool touch = w00 != 0.0f || w01 != 0.0f || w10 != 0.0f || w11 != 0.0f;
       if (a.channels_last && (a.C & 3) == 0) {

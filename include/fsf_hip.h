@@ -790,6 +790,28 @@ int fsf_project_gather_bilinear(const float* xyz, int64_t n, int32_t xyz_stride,
                                 const float* feat, int32_t channels, int32_t feat_h, int32_t feat_w, int32_t channels_last,
                                 int32_t img_h, int32_t img_w, int32_t reduce_cams, float* out, uint8_t* count, void* stream);
 
+/* K13c  backward of K13b with respect to the feature map: the exact transpose of the gather above, i.e. what autograd computes for
+ * prj_points_2d (FSF.py:169-226 is the call site's projection and sampling) followed by F.grid_sample's backward for its input
+ * (grid_sampler_2d_backward, bilinear, align_corners=False, zeros), but as a sorted gather instead of a float-atomic scatter: no float
+ * atomics, bit-identical from run to run, no host wait.  The taps are K13b's, bit for bit (csrc/bilinear_taps.h):
+ *   grad_feat[cam, :, y, x] = sum over every (point i, corner k) that lands on the texel of a_k(i, cam) * grad_out[i, cam, :]
+ * with a_k = wx * wy of the corner, zero for corners outside the map and for invalid projections.  No gradient for xyz / lidar2img.
+ *   grad_out   f32 [n, ncam, channels] (reduce_cams = 0) or [n, channels] (reduce_cams = 1: the row is shared by the cameras that see
+ *              the point), contiguous
+ *   grad_feat  f32 [ncam, channels, feat_h, feat_w] (channels_last = 0) or [ncam, feat_h, feat_w, channels] (channels_last = 1): EVERY
+ *              element is written, zeros included, whatever the buffer held; n = 0 gives the all-zero map
+ *   workspace  fsf_project_gather_bilinear_backward_workspace_bytes(n, ncam, feat_h, feat_w, channels) bytes, contents undefined
+ * A texel's taps are summed in fp32 in the order (corner 00, 01, 10, 11; within a corner, entries i * ncam + cam ascending), a corner's
+ * run longer than FSF_BILINEAR_BWD_CHUNK entries in chunks of that length whose partial sums are added in chunk order.
+ * FSF_ERR_INVALID_ARG under K13b's rules; FSF_ERR_UNSUPPORTED when n * ncam >= 2^32 or ncam (feat_h + 1)(feat_w + 1) >= 2^31 (the
+ * size function answers 0 to both); FSF_ERR_WORKSPACE when the workspace is short. */
+#define FSF_BILINEAR_BWD_CHUNK 128
+int64_t fsf_project_gather_bilinear_backward_workspace_bytes(int64_t n, int32_t ncam, int32_t feat_h, int32_t feat_w, int32_t channels);
+int fsf_project_gather_bilinear_backward(const float* xyz, int64_t n, int32_t xyz_stride, const float* lidar2img, int32_t ncam,
+                                         const float* grad_out, int32_t channels, int32_t feat_h, int32_t feat_w,
+                                         int32_t channels_last, int32_t img_h, int32_t img_w, int32_t reduce_cams, float* grad_feat,
+                                         void* workspace, int64_t workspace_bytes, void* stream);
+
 /* K16  camera select + 2-D prediction lookup for the per-point branch (nuScenes: score column only).
  * Replaces: FSF.img_cross_attn cam-select (FSF.py:716-718) + get_all_cls_preds_2d (:506-535) +
  *   encode_preds_2d(encode_single_cls=False) (:449-474) for one batch sample:
