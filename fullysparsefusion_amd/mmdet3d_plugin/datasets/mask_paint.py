@@ -23,8 +23,11 @@ Detections come in two forms:
     segm_result[i] n masks of the camera's image size (a class with no masks is skipped, as the writer does);
   * packed (`dict`): boxes [N, 4], scores [N], labels [N] (nuImages index), cams [N] and either `masks` (full image size: one
     [N, H, W] array / tensor, or a list of N 2-D masks, host or device), or `mask_crops` (N 2-D arrays) with `mask_origins` [N, 2]
-    (y, x), or neither (bbox_only).  Boxes and scores are taken as float32.
+    (y, x), or `mask_rois` (what a mask head emits: one [N, M, M] float32 / float16 array or tensor of soft masks, host or
+    device, pasted over each box by `roi_cover`'s rule: K34c), or none of them (bbox_only).  Boxes and scores are taken as float32.
 """
+import math
+
 import numpy as np
 import torch
 
@@ -103,6 +106,27 @@ def _checked_len(dets, n):
         raise ValueError(f"mask detections: {len(dets['mask_crops'])} mask crops for {n} boxes")
 
 
+ROI_MAX = 64  # the largest RoI map side K34c takes (a mask head's is 14 or 28)
+
+
+def _checked_rois(dets, n):
+    """`mask_rois` excludes the two other mask forms and is one float32 / float16 [n, M, M] array or tensor, 1 <= M <= ROI_MAX."""
+    rois = dets.get("mask_rois")
+    if rois is None:
+        return
+    for other in ("masks", "mask_crops"):
+        if dets.get(other) is not None:
+            raise ValueError(f"mask detections: mask_rois and {other} are both given, pass one form of masks")
+    shape = tuple(getattr(rois, "shape", ()))
+    if not isinstance(rois, (np.ndarray, torch.Tensor)) or len(shape) != 3 or shape[1] != shape[2] or not 1 <= shape[1] <= ROI_MAX:
+        raise ValueError(f"mask detections: mask_rois must be one [N, M, M] array or tensor with 1 <= M <= {ROI_MAX}, "
+                         f"got {type(rois).__name__} of shape {shape}")
+    if str(rois.dtype).split(".")[-1] not in ("float32", "float16"):
+        raise ValueError(f"mask detections: mask_rois must be float32 or float16, got {rois.dtype}")
+    if shape[0] != n:
+        raise ValueError(f"mask detections: {shape[0]} mask_rois for {n} boxes")
+
+
 def paint_order(scores, groups):
     """Indices of `scores` grouped by `groups` (ascending), each group by descending score, equal scores later index first."""
     scores = np.asarray(scores, dtype=np.float64)
@@ -116,11 +140,14 @@ def score_threshold(scores, topk, score_thr_init):
     return max(float(s[topk - 1]) if len(s) >= topk else 0.0, float(score_thr_init))
 
 
-def plan_masks(dets, is_argo=False, class_names=None, img_shapes=None, score_thr_init=None, topk=None, bbox_only=False):
+def plan_masks(dets, is_argo=False, class_names=None, img_shapes=None, score_thr_init=None, topk=None, bbox_only=False, mask_thr=0.5):
     """Selection, paint order, ids, output planes and anno rows (the anno.json structure) of one frame.  `dets`: packed dict or
-    mmdet's per-camera list.  Scores on the device cost one read-back; nothing else is read from the device here."""
+    mmdet's per-camera list.  Scores on the device cost one read-back; nothing else is read from the device here.  `mask_thr`: the
+    threshold on pasted `mask_rois` (mmdet's mask_thr_binary), taken as float32."""
     if not isinstance(dets, dict):
         dets = pack_mmdet(dets)
+    if not float(mask_thr) > 0.0:
+        raise ValueError(f"mask_thr must be above 0, got {mask_thr}: a threshold of 0 or less covers every pixel the paste leaves at 0")
     ds = "argo" if is_argo else "nuscenes"
     score_thr_init = DEFAULTS[ds]["score_thr_init"] if score_thr_init is None else score_thr_init
     topk = DEFAULTS[ds]["topk"] if topk is None else int(topk)
@@ -129,6 +156,8 @@ def plan_masks(dets, is_argo=False, class_names=None, img_shapes=None, score_thr
     scores = small["scores"].astype(np.float32).reshape(-1)
     n = len(scores)
     _checked_len(dets, n)
+    if not bbox_only:
+        _checked_rois(dets, n)
     boxes = small["boxes"].astype(np.float32).reshape(n, 4)
     labels = small["labels"].astype(np.int64).reshape(n)
     cams = small["cams"].astype(np.int64).reshape(n)
@@ -184,7 +213,7 @@ def plan_masks(dets, is_argo=False, class_names=None, img_shapes=None, score_thr
     # the planner emits rows plane by plane in paint order: a stable sort by plane keeps the order inside each plane
     by_plane = np.argsort(obj_plane, kind="stable")
     return MaskPlan(is_argo=is_argo, dets=dets, boxes=boxes, cams=cams, img_shapes=img_shapes, planes_src=planes_src, dst=dst,
-                    bbox_only=bool(bbox_only), threshold=thr, anno=anno, num_painted=len(painted),
+                    bbox_only=bool(bbox_only), mask_thr=np.float32(mask_thr), threshold=thr, anno=anno, num_painted=len(painted),
                     obj_index=obj_index[by_plane], obj_plane=obj_plane[by_plane], obj_id=obj_id[by_plane],
                     class_names=class_names)
 
@@ -206,13 +235,90 @@ def _nonzero_crop(mask):
     return int(y0), int(x0), np.ascontiguousarray(mask[y0:y1, x0:x1]).astype(np.uint8)
 
 
+def roi_rect(box, shape):
+    """(y0, x0, h, w) of the pixels `roi_cover` looks at: rows [max(floor(y0) - 1, 0), min(ceil(y1) + 1, H)), columns likewise
+    (mmdet's per-object paste window); (0, 0, 0, 0) for a box that is not finite or has x1 <= x0 or y1 <= y0."""
+    x0, y0, x1, y1 = (float(np.float32(v)) for v in box)
+    if not all(math.isfinite(v) for v in (x0, y0, x1, y1)) or x1 <= x0 or y1 <= y0:
+        return 0, 0, 0, 0
+    ya, yb = max(math.floor(y0) - 1, 0), min(math.ceil(y1) + 1, int(shape[0]))
+    xa, xb = max(math.floor(x0) - 1, 0), min(math.ceil(x1) + 1, int(shape[1]))
+    if yb <= ya or xb <= xa:
+        return 0, 0, 0, 0
+    return ya, xa, yb - ya, xb - xa
+
+
+def _roi_taps(centres, lo, hi, m):
+    """One axis of `roi_cover`: pixel indices -> (texel index + 1 into a zero-padded map, weight of that texel, weight of the next,
+    usable).  Float32, one rounding per operation.  A pixel whose first tap is not in [-1, m) touches no texel: not usable."""
+    f = np.float32
+    with np.errstate(all="ignore"):
+        g = ((centres.astype(f) + f(0.5)) - lo) / (hi - lo) * f(2.0) - f(1.0)
+        i = ((g + f(1.0)) * f(m) - f(1.0)) * f(0.5)
+        i0 = np.floor(i)
+        w1 = i - i0
+        w0 = f(1.0) - w1
+        ok = (i0 >= f(-1.0)) & (i0 < f(m))  # (False for NaN)
+    return np.where(ok, i0, f(-1.0)).astype(np.int64) + 1, w0, w1, ok
+
+
+def roi_cover(box, roi, thr, shape):
+    """The host specification of K34c: mmdet's `_do_paste_mask` + `mask_thr_binary` for one object on an image of `shape`, i.e.
+    F.grid_sample(bilinear, align_corners=False, zero padding) of the RoI map `roi` [M, M] over the float32 box (x0, y0, x1, y1),
+    thresholded.  Returns (y0, x0, h, w, cover): the candidate rectangle (`roi_rect`) and a bool [h, w] of its covered pixels.
+    Float32, one rounding per operation, no contraction, fixed order; for pixel (py, px):
+        gx = ((px + 0.5) - x0) / (x1 - x0) * 2 - 1;  ix = ((gx + 1) * M - 1) * 0.5;  ix0 = floor(ix);  wx1 = ix - ix0;  wx0 = 1 - wx1
+        v  = m[iy0, ix0] * (wx0 * wy0) + m[iy0, ix0 + 1] * (wx1 * wy0) + m[iy0 + 1, ix0] * (wx0 * wy1) + m[iy0 + 1, ix0 + 1] * (wx1 * wy1)
+    summed left to right, a texel outside the map counting 0; covered iff v >= thr (never for a NaN).  A float16 map is widened
+    exactly."""
+    ya, xa, h, w, v, usable = roi_sample(box, roi, shape)
+    with np.errstate(invalid="ignore"):
+        return ya, xa, h, w, (v >= np.float32(thr)) & usable
+
+
+def roi_sample(box, roi, shape):
+    """`roi_cover` before its threshold: (y0, x0, h, w, v float32 [h, w], usable bool [h, w]); a pixel that is not usable touches no
+    texel (its v is meaningless and it is never covered)."""
+    f = np.float32
+    ya, xa, h, w = roi_rect(box, shape)
+    if h == 0:
+        return 0, 0, 0, 0, np.zeros((0, 0), f), np.zeros((0, 0), bool)
+    roi = np.asarray(roi)
+    m = roi.shape[0]
+    assert roi.shape == (m, m)
+    x0, y0, x1, y1 = (f(v) for v in box)
+    pad = np.zeros((m + 2, m + 2), f)
+    pad[1:-1, 1:-1] = roi.astype(f)
+    iy, wy0, wy1, oky = _roi_taps(np.arange(ya, ya + h), y0, y1, m)
+    ix, wx0, wx1, okx = _roi_taps(np.arange(xa, xa + w), x0, x1, m)
+    iy, wy0, wy1, ix, wx0, wx1 = iy[:, None], wy0[:, None], wy1[:, None], ix[None, :], wx0[None, :], wx1[None, :]
+    with np.errstate(all="ignore"):
+        v = pad[iy, ix] * (wx0 * wy0)
+        v = v + pad[iy, ix + 1] * (wx1 * wy0)
+        v = v + pad[iy + 1, ix] * (wx0 * wy1)
+        v = v + pad[iy + 1, ix + 1] * (wx1 * wy1)
+    assert v.dtype == f
+    return ya, xa, h, w, v, oky[:, None] & okx[None, :]
+
+
+def paste_roi_mask(box, roi, thr, shape):
+    """`roi_cover` as a full-size bool mask [H, W] (what mmdet's paste hands the offline writer)."""
+    ya, xa, h, w, cover = roi_cover(box, roi, thr, shape)
+    out = np.zeros(tuple(int(v) for v in shape), bool)
+    out[ya:ya + h, xa:xa + w] = cover
+    return out
+
+
 def _mask_form(plan):
-    """'rect' (bbox_only), 'crops', 'device' (full-size device masks) or 'host' (full-size host masks)."""
+    """'rect' (bbox_only), 'crops', 'rois' (RoI maps pasted over the boxes), 'device' (full-size device masks) or 'host' (full-size
+    host masks)."""
     d = plan.dets
     if plan.bbox_only:
         return "rect"
     if d.get("mask_crops") is not None:
         return "crops"
+    if d.get("mask_rois") is not None:
+        return "rois"
     masks = d.get("masks")
     if masks is None:
         raise ValueError("mask detections carry no masks: pass masks / mask_crops, or bbox_only=True")
@@ -229,11 +335,16 @@ def _check_full(plan, k, shape):
 def host_geometry(plan):
     """Per painted row (y0, x0, crop) with crop a u8 2-D array, or None for a solid rectangle (bbox_only)."""
     form, d, out = _mask_form(plan), plan.dets, []
+    rois = _host(d["mask_rois"]) if form == "rois" and len(plan.obj_index) else None
     for k in plan.obj_index:
         shape = plan.img_shapes[int(plan.cams[k])]
         if form == "rect":
             y0, x0, h, w = bbox_rect(plan.boxes[k], shape)
             out.append((y0, x0, h, w, None))
+            continue
+        if form == "rois":
+            y0, x0, h, w, cover = roi_cover(plan.boxes[k], rois[k], plan.mask_thr, shape)
+            out.append((y0, x0, h, w, cover.astype(np.uint8)))
             continue
         if form == "crops":
             crop = np.asarray(_host(d["mask_crops"][k])).astype(np.uint8)
@@ -307,6 +418,8 @@ def paint_device(plan, device):
 
     device = torch.device(device)
     form, m = _mask_form(plan), len(plan.obj_index)
+    if form == "rois":
+        return _paint_device_rois(plan, device)
     pitch, src_off = np.zeros(m, np.int64), np.zeros(m, np.int64)
     rects, ext_row = np.zeros((m, 4), np.int64), np.full(m, -1, np.int64)
     masks_dev, groups = None, []
@@ -369,27 +482,67 @@ def paint_device(plan, device):
                                         torch.int32 if plan.is_argo else torch.uint8, masks=masks_dev, extents=extents)
 
 
+def _paint_device_rois(plan, device):
+    """K34c (fsf_paint_roi_masks): the `mask_rois` form painted in one launch, no full-size mask in between.  Table rows carry the
+    candidate rectangle (`roi_rect`) and point into the RoI buffer by element offset: a device tensor is read where it lies (painted
+    rows only, no gather copy), host maps of the painted rows ride in the table's one pinned upload.  K34a does not run; no host wait."""
+    from ... import hip_ops_mask
+
+    m, rois = len(plan.obj_index), plan.dets["mask_rois"]
+    side = int(rois.shape[1])
+    rects = np.zeros((m, 4), np.int64)
+    for r, k in enumerate(plan.obj_index):
+        rects[r] = roi_rect(plan.boxes[k], plan.img_shapes[int(plan.cams[k])])
+    num_planes = len(plan.planes_src)
+    table = np.zeros((m, 8), dtype=np.int32)
+    table[:, 0], table[:, 1:5], table[:, 6], table[:, 7] = plan.obj_plane, rects, -1, plan.obj_id
+    plane_ptr = np.searchsorted(plan.obj_plane, np.arange(num_planes + 1)).astype(np.int32)
+    src_hw = np.asarray(plan.planes_src, dtype=np.int32).reshape(num_planes, 2)
+    scale = (src_hw / np.asarray(plan.dst, dtype=np.float64)).astype(np.float32)  # f32(h / dst_h): _resize_nearest's factor
+    boxes = np.ascontiguousarray(plan.boxes[plan.obj_index], dtype=np.float32).reshape(m, 4)
+    arrays = [None, table, plane_ptr, src_hw, scale, boxes]
+    dtypes = [torch.int64, torch.int32, torch.int32, torch.int32, torch.float32, torch.float32]
+    if isinstance(rois, torch.Tensor) and rois.is_cuda:
+        rois_dev = rois.detach().to(device).contiguous()
+        arrays[0] = plan.obj_index.astype(np.int64) * (side * side)
+    else:
+        picked = np.ascontiguousarray(_host(rois)[plan.obj_index]).reshape(m, side, side)
+        arrays[0] = np.arange(m, dtype=np.int64) * (side * side)
+        arrays.append(picked)
+        dtypes.append(torch.float16 if picked.dtype == np.float16 else torch.float32)
+    views = _upload(arrays, dtypes, device)
+    if len(views) == 7:
+        rois_dev = views[6]
+    d_off, d_table, d_ptr, d_hw, d_scale, d_boxes = views[:6]
+    return hip_ops_mask.paint_roi_masks(d_table.view(-1, 8), d_boxes.view(-1, 4), d_off, d_ptr, d_hw, d_scale, plan.dst,
+                                        torch.int32 if plan.is_argo else torch.uint8, rois_dev, side, float(plan.mask_thr))
+
+
 @PIPELINES.register_module(force=True)
 class PaintMasksFromDetections:
     """`mask_data` / `mask_anno` from `results["mask_detections"]` (a 2-D segmenter's output of this frame), equal to what
     LoadMaskFromFiles returns for the reference writer's files.  Argoverse 2 also reads `results["mask_img_shapes"]` (the (h, w) of
     each camera image; or `img_shapes` in the packed detections) and scales lidar2img[0] as load_argo does.  `device`: paint with
-    K34 on that device (mask_data stays there); None: the host painter."""
+    K34 on that device (mask_data stays there); None: the host painter.  `mask_thr`: the threshold on pasted `mask_rois` (mmdet's
+    mask_thr_binary)."""
 
     def __init__(self, class_names=["car", "truck", "trailer", "bus", "construction_vehicle", "bicycle", "motorcycle", "pedestrian",
                                      "traffic_cone", "barrier"], obj_max_num=250, is_argo=False, is_waymo=False, score_thr_init=None,
-                 topk=None, bbox_only=False, device=None):
+                 topk=None, bbox_only=False, device=None, mask_thr=0.5):
         if is_waymo:
             raise NotImplementedError("Waymo: the reference has no mask writer to reproduce")
         self.loader = LoadMaskFromFiles(None, class_names=class_names, obj_max_num=obj_max_num, is_argo=is_argo)
         self.class_names, self.is_argo = class_names, is_argo
         self.score_thr_init, self.topk, self.bbox_only, self.device = score_thr_init, topk, bbox_only, device
+        if not float(mask_thr) > 0.0:
+            raise ValueError(f"mask_thr must be above 0, got {mask_thr}")
+        self.mask_thr = mask_thr
 
     def plan(self, results):
         dets = results["mask_detections"]
         shapes = results.get("mask_img_shapes", dets.get("img_shapes") if isinstance(dets, dict) else None)
         return plan_masks(dets, is_argo=self.is_argo, class_names=self.class_names, img_shapes=shapes,
-                          score_thr_init=self.score_thr_init, topk=self.topk, bbox_only=self.bbox_only)
+                          score_thr_init=self.score_thr_init, topk=self.topk, bbox_only=self.bbox_only, mask_thr=self.mask_thr)
 
     def __call__(self, results):
         plan = self.plan(results)

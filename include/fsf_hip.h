@@ -515,12 +515,32 @@ int fsf_train_augment_boxes(const float* boxes, int64_t box_stride, int32_t box_
  *   out         u8 (out_elem_bytes 1; ids above 255 keep their low byte: the caller checks) or i32 (4) [num_planes, dst_h, dst_w],
  *               16-byte aligned, dst_w % 16 == 0.  Every element is written exactly once (no memset needed).
  * The caller guarantees every rectangle lies inside its mask's source.  Nothing here synchronises.
+ * K34c fsf_paint_roi_masks: the same planes from a mask head's RoI outputs, pasted on the fly (mmdet 2.x _do_paste_mask +
+ *   mask_thr_binary; mmdet3d_plugin/datasets/mask_paint.py roi_cover is the host specification, bit for bit).  One launch.
+ *   table       as K34b; (y0, x0, h, w) is the row's CANDIDATE rectangle in source pixels, rows [max(floor(by0) - 1, 0),
+ *               min(ceil(by1) + 1, src_h)) and columns likewise (h = w = 0 for a box that is not finite or not positive: nothing
+ *               painted); pixels outside it are not covered.  pitch and ext_row are not read.
+ *   boxes       f32 [n_rows, 4] device: (bx0, by0, bx1, by1) of each row, source pixels
+ *   roi_off     i64 [n_rows] device: ELEMENT offset of the row's map in rois (rows may share or skip maps; only these are read)
+ *   rois        f32 (roi_elem_bytes 4) or f16 (2, widened exactly) maps of roi_size x roi_size (M, 1 <= M <= 64), row-major
+ *   Source pixel (py, px) of a row is covered iff v >= thr (thr > 0; never for a NaN), in f32 with one rounding per operation:
+ *               gx = ((px + 0.5) - bx0) / (bx1 - bx0) * 2 - 1;  ix = ((gx + 1) * M - 1) * 0.5;  ix0 = floor(ix);  wx1 = ix - ix0;
+ *               wx0 = 1 - wx1 (likewise y);  v = m[iy0][ix0] * (wx0 * wy0) + m[iy0][ix0 + 1] * (wx1 * wy0) + m[iy0 + 1][ix0] *
+ *               (wx0 * wy1) + m[iy0 + 1][ix0 + 1] * (wx1 * wy1), summed left to right, a texel outside the map counting 0
+ *               (F.grid_sample bilinear, align_corners=False, zero padding: the tap rule of csrc/bilinear_taps.h).
+ *   plane_ptr, plane_src_hw, plane_scale, out, dst_h, dst_w, out_elem_bytes: as K34b (the rule is evaluated at the source pixel of
+ *               each output pixel; every output element is written exactly once).
+ *   The caller guarantees roi_off[r] + M * M <= the element count of rois.  Nothing here synchronises.
  */
 int fsf_mask_extents(const uint8_t* masks, int64_t n_masks, int32_t h, int32_t w, const int32_t* mask_index, int64_t n_out,
                      int32_t* out, int64_t out_stride, void* stream);
 int fsf_paint_instance_masks(const int32_t* table, const int64_t* src_off, int64_t n_rows, const int32_t* plane_ptr,
                              const int32_t* plane_src_hw, const float* plane_scale, int32_t num_planes, const int32_t* extents,
                              const uint8_t* masks, int32_t dst_h, int32_t dst_w, int32_t out_elem_bytes, void* out, void* stream);
+int fsf_paint_roi_masks(const int32_t* table, const float* boxes, const int64_t* roi_off, int64_t n_rows, const int32_t* plane_ptr,
+                        const int32_t* plane_src_hw, const float* plane_scale, int32_t num_planes, const void* rois, int32_t roi_size,
+                        int32_t roi_elem_bytes, float thr, int32_t dst_h, int32_t dst_w, int32_t out_elem_bytes, void* out,
+                        void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * K35  segmentation-head targets and losses (docs/kernels/K35_seg_losses.md)
