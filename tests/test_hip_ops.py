@@ -12,6 +12,7 @@ from oracle import refine as orefine
 from oracle import scatter as oscatter
 from oracle import spconv as osp
 from oracle import voxelize as ovox
+from project_cases import overlap_rows_reference
 
 pytestmark = pytest.mark.gpu
 
@@ -403,24 +404,6 @@ def test_group_pairs_equal_the_torch_expression(ops, device, n, ng, empty_group,
         want3 = fg3.t().nonzero(as_tuple=False)
         g3, p3 = ops.group_pairs(cls, th, keep_one=True, group_cols=cols)
         assert torch.equal(g3, want3[:, 0]) and torch.equal(p3, want3[:, 1])
-
-
-def overlap_rows_reference(obj):
-    """extract_fg_pts + double_overlap_pts + get_sir_coors of the reference (FSF.py:299-308, :260-297, :373-376) on an [n, cells]
-    id tensor, as index lists: (src_pt, id) per output row."""
-    fg_idx = (obj.sum(-1) > 0).nonzero().squeeze(1)
-    rows = obj[fg_idx]
-    k = (rows > 0).sum(-1)
-    src, ids = [fg_idx], [rows.max(-1)[0]]
-    for kk in range(2, int(k.max()) + 1 if k.numel() else 0):
-        sel = k == kk
-        if int(sel.sum()) == 0:
-            continue
-        top = rows[sel].topk(kk, dim=-1)[0]
-        for j in range(1, kk):
-            src.append(fg_idx[sel])
-            ids.append(top[:, j])
-    return torch.cat(src), torch.cat(ids)
 
 
 @pytest.mark.parametrize("case", ["frame_like", "dense_overlaps", "no_foreground", "int32_masks"])
