@@ -94,9 +94,15 @@ struct AsOut {
 
 using namespace fsf;
 
-extern "C" int64_t fsf_assemble_sweeps_workspace_bytes(int64_t n_rows) {
-  return fsf_align_up(scan_num_tiles(n_rows) * 4, 256) + 256 + fsf_align_up((int64_t)sizeof(AsArgs), 256);
-}
+struct AsLayout {
+  uint32_t* tile_sums;
+  int64_t* total;
+  AsArgs* a_dev;
+  AsLayout(FsfArena& arena, int64_t n_rows)
+      : tile_sums(arena.take<uint32_t>(scan_num_tiles(n_rows))), total(arena.take<int64_t>(1)), a_dev(arena.take<AsArgs>(1)) {}
+};
+
+extern "C" int64_t fsf_assemble_sweeps_workspace_bytes(int64_t n_rows) { return fsf_layout_bytes<AsLayout>(n_rows); }
 
 extern "C" int fsf_assemble_sweeps(const float* raw, int64_t n_rows, int32_t load_dim, const int64_t* sweep_offsets, int32_t num_sweeps,
                                    const double* sweep_params, const uint8_t* sweep_transform, const uint8_t* sweep_remove_close,
@@ -108,7 +114,7 @@ extern "C" int fsf_assemble_sweeps(const float* raw, int64_t n_rows, int32_t loa
       !sweep_transform || !sweep_remove_close || norm_col >= load_dim || (norm_col >= 0 && norm_std == 0.0f) ||
       (n_rows > 0 && (!raw || !out)) || (!count_dev && !count_host))
     return FSF_ERR_INVALID_ARG;
-  if (!workspace || workspace_bytes < fsf_assemble_sweeps_workspace_bytes(n_rows)) return FSF_ERR_WORKSPACE;
+  FSF_CARVE(AsLayout, l, workspace, workspace_bytes, n_rows);
   AsArgs a;
   a.raw = raw; a.out = out; a.n = n_rows;
   a.load_dim = load_dim; a.out_dim = load_dim + 3; a.nsweeps = num_sweeps; a.norm_col = norm_col;
@@ -123,14 +129,9 @@ extern "C" int fsf_assemble_sweeps(const float* raw, int64_t n_rows, int32_t loa
     a.transform[s] = sweep_transform[s];
     a.remove_close[s] = sweep_remove_close[s];
   }
-  FsfArena arena(workspace, workspace_bytes);
-  uint32_t* tile_sums = arena.take<uint32_t>(scan_num_tiles(n_rows));
-  int64_t* total = arena.take<int64_t>(1);
-  AsArgs* a_dev = reinterpret_cast<AsArgs*>(arena.take<char>((int64_t)sizeof(AsArgs)));
-  if (!arena.ok()) return FSF_ERR_WORKSPACE;
-  int64_t* tot = count_dev ? count_dev : total;
-  FSF_HIP_TRY(hipMemcpyAsync(a_dev, &a, sizeof(AsArgs), hipMemcpyHostToDevice, stream));  // (pageable source: staged before the call returns)
-  int rc = exclusive_scan_u32(AsIn{a_dev}, AsOut{a_dev}, n_rows, tile_sums, nullptr, tot, stream);
+  int64_t* tot = count_dev ? count_dev : l.total;
+  FSF_HIP_TRY(hipMemcpyAsync(l.a_dev, &a, sizeof(AsArgs), hipMemcpyHostToDevice, stream));  // (pageable source: staged before the call returns)
+  int rc = exclusive_scan_u32(AsIn{l.a_dev}, AsOut{l.a_dev}, n_rows, l.tile_sums, nullptr, tot, stream);
   if (rc != FSF_OK) return rc;
   if (count_host) {
     FSF_READ_BACK(count_host, tot, sizeof(int64_t), stream);

@@ -149,9 +149,17 @@ using namespace fsf;
 
 extern "C" int32_t fsf_augment_max(void) { return AUG_MAX; }
 
+struct AugLayout {
+  uint32_t* tile_sums;
+  int64_t* tot;
+  AugArgs* a_dev;
+  AugLayout(FsfArena& arena, int64_t total)
+      : tile_sums(arena.take<uint32_t>(scan_num_tiles(total))), tot(arena.take<int64_t>(1)), a_dev(arena.take<AugArgs>(1)) {}
+};
+
 extern "C" int64_t fsf_augment_points_workspace_bytes(int64_t n_rows, int32_t num_augs) {
   if (n_rows < 0 || num_augs < 1) return 0;
-  return fsf_align_up(scan_num_tiles(n_rows * num_augs) * 4, 256) + 256 + fsf_align_up((int64_t)sizeof(AugArgs), 256);
+  return fsf_layout_bytes<AugLayout>(n_rows * num_augs);
 }
 
 extern "C" int fsf_augment_points(const float* points, int64_t n_rows, int32_t cols, const float* aug_desc, int32_t num_augs,
@@ -163,20 +171,15 @@ extern "C" int fsf_augment_points(const float* points, int64_t n_rows, int32_t c
   AugArgs a;
   const int rc0 = aug_fill_descs(a, aug_desc, num_augs);
   if (rc0 != FSF_OK) return rc0;
-  if (!workspace || workspace_bytes < fsf_augment_points_workspace_bytes(n_rows, num_augs)) return FSF_ERR_WORKSPACE;
+  const int64_t total = n_rows * num_augs;
+  FSF_CARVE(AugLayout, l, workspace, workspace_bytes, total);
   a.in = points; a.out = out; a.offsets = offsets_dev; a.n = n_rows; a.cols = cols;
   a.use_range = pc_range ? 1 : 0;
   for (int k = 0; k < 6; ++k) a.range[k] = pc_range ? pc_range[k] : 0.0f;
-  FsfArena arena(workspace, workspace_bytes);
-  const int64_t total = n_rows * num_augs;
-  uint32_t* tile_sums = arena.take<uint32_t>(scan_num_tiles(total));
-  int64_t* tot = arena.take<int64_t>(1);
-  AugArgs* a_dev = reinterpret_cast<AugArgs*>(arena.take<char>((int64_t)sizeof(AugArgs)));
-  if (!arena.ok()) return FSF_ERR_WORKSPACE;
   FSF_HIP_TRY(hipMemsetAsync(offsets_dev, 0, sizeof(int64_t) * (num_augs + 1), stream));
-  FSF_HIP_TRY(hipMemcpyAsync(a_dev, &a, sizeof(AugArgs), hipMemcpyHostToDevice, stream));  // (pageable source: staged before return)
+  FSF_HIP_TRY(hipMemcpyAsync(l.a_dev, &a, sizeof(AugArgs), hipMemcpyHostToDevice, stream));  // (pageable source: staged before return)
   if (total > 0) {
-    const int rc = exclusive_scan_u32(AugIn{a_dev}, AugOut{a_dev}, total, tile_sums, nullptr, tot, stream);
+    const int rc = exclusive_scan_u32(AugIn{l.a_dev}, AugOut{l.a_dev}, total, l.tile_sums, nullptr, l.tot, stream);
     if (rc != FSF_OK) return rc;
   }
   if (offsets_host) {

@@ -170,9 +170,7 @@ extern "C" int fsf_decode_cluster_boxes(const float* cls_logits, int64_t cls_str
 
 extern "C" int64_t fsf_class_rank_desc_workspace_bytes(int64_t n, int32_t num_classes) {
   if (n < 0 || num_classes < 1) return 0;
-  const int64_t total = n * num_classes;
-  return 2 * fsf_align_up(total * 8, 256) + 2 * fsf_align_up(total * 4, 256) +
-         fsf_align_up((int64_t)RS_BINS * (radix_num_tiles(total) + 1) * 4, 256) + 1024;
+  return radix_sort_scratch_bytes(n * num_classes);  // (the sort's scratch is all the entry takes)
 }
 
 extern "C" int fsf_class_rank_desc(const float* scores_t, int64_t n, int32_t num_classes, float score_thr, int32_t* order,
@@ -183,17 +181,11 @@ extern "C" int fsf_class_rank_desc(const float* scores_t, int64_t n, int32_t num
   FSF_HIP_TRY(hipMemsetAsync(count, 0, sizeof(int32_t) * num_classes, stream));
   if (n == 0) return FSF_OK;
   const int64_t total = n * num_classes;
-  FsfArena arena(workspace, workspace_bytes);
-  uint64_t* ka = arena.take<uint64_t>(total);
-  uint64_t* kb = arena.take<uint64_t>(total);
-  uint32_t* va = arena.take<uint32_t>(total);
-  uint32_t* vb = arena.take<uint32_t>(total);
-  uint32_t* hist = arena.take<uint32_t>((int64_t)RS_BINS * (radix_num_tiles(total) + 1));
-  if (!ka || !kb || !va || !vb || !hist) return FSF_ERR_WORKSPACE;
-  hipLaunchKernelGGL(bt_keys_kernel, dim3(fsf_stream_grid(total, 256)), dim3(256), 0, stream, scores_t, total, n, score_thr, ka, va);
+  FSF_CARVE(RadixScratch, s, workspace, workspace_bytes, total);
+  hipLaunchKernelGGL(bt_keys_kernel, dim3(fsf_stream_grid(total, 256)), dim3(256), 0, stream, scores_t, total, n, score_thr, s.keys_a, s.vals_a);
   uint64_t* sk;
   uint32_t* sv;
-  const int rc = radix_sort_pairs(ka, va, kb, vb, hist, total, 32 + bt_class_bits(num_classes), &sk, &sv, stream);
+  const int rc = radix_sort_pairs(s.keys_a, s.vals_a, s.keys_b, s.vals_b, s.hist, total, 32 + bt_class_bits(num_classes), &sk, &sv, stream);
   if (rc != FSF_OK) return rc;
   hipLaunchKernelGGL(bt_rank_kernel, dim3(fsf_stream_grid(total, 256)), dim3(256), 0, stream, sk, sv, total, n, order, rank, count);
   FSF_LAUNCH_CHECK();

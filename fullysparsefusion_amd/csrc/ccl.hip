@@ -218,12 +218,21 @@ __global__ void __launch_bounds__(256)
 
 using namespace fsf;
 
+struct CclLayout {
+  int *parent, *rank;
+  uint32_t* tile_sums;
+  int2* tile_range;  // only with a distance table
+  float4* tile_box;
+  float* tile_dmax;
+  CclLayout(FsfArena& ar, int64_t n, int64_t tiles, bool with_table)
+      : parent(ar.take<int>(n)), rank(ar.take<int>(n)), tile_sums(ar.take<uint32_t>(scan_num_tiles(n))),
+        tile_range(with_table ? ar.take<int2>(tiles) : nullptr), tile_box(ar.take<float4>(tiles)), tile_dmax(ar.take<float>(tiles)) {}
+};
 
 extern "C" int64_t fsf_connected_components_workspace_bytes(int64_t n) {
   const int64_t nn = n > 0 ? n : 1;
   const int64_t tiles = (nn + 255) / 256;
-  return fsf_align_up(nn * 4, 256) * 2 + fsf_align_up(scan_num_tiles(n) * 4, 256) + fsf_align_up(tiles * 8, 256) +
-         fsf_align_up(tiles * 16, 256) + fsf_align_up(tiles * 4, 256) + 256;
+  return fsf_layout_bytes<CclLayout>(nn, tiles, true);
 }
 
 static int ccl_run(const float* points, int64_t n, int32_t point_stride, const int32_t* batch_idx, float dist,
@@ -235,31 +244,23 @@ static int ccl_run(const float* points, int64_t n, int32_t point_stride, const i
     if (num_components_dev) FSF_HIP_TRY(hipMemsetAsync(num_components_dev, 0, sizeof(int64_t), stream));
     return FSF_OK;
   }
-  if (workspace_bytes < fsf_connected_components_workspace_bytes(n)) return FSF_ERR_WORKSPACE;
-  FsfArena ar(workspace, workspace_bytes);
-  int* parent = ar.take<int>(n);
-  int* rank = ar.take<int>(n);
-  uint32_t* tile_sums = ar.take<uint32_t>(scan_num_tiles(n));
   const int64_t tiles = (n + 255) / 256;
-  int2* tile_range = dist_table ? ar.take<int2>(tiles) : nullptr;
-  float4* tile_box = ar.take<float4>(tiles);
-  float* tile_dmax = ar.take<float>(tiles);
-  if (!ar.ok()) return FSF_ERR_WORKSPACE;
+  FSF_CARVE(CclLayout, l, workspace, workspace_bytes, n, tiles, dist_table != nullptr);
   const int grid = fsf_stream_grid(n, 256);
-  hipLaunchKernelGGL(ccl_init_kernel, dim3(grid), dim3(256), 0, stream, parent, n);
+  hipLaunchKernelGGL(ccl_init_kernel, dim3(grid), dim3(256), 0, stream, l.parent, n);
   if (tiles > 65535) return FSF_ERR_UNSUPPORTED;  // (gridDim.y; 16.7 M points)
   hipLaunchKernelGGL(ccl_tile_range_kernel, dim3((unsigned)tiles), dim3(256), 0, stream, points, (int)point_stride,
-                     dist_table ? batch_idx : nullptr, n, dist, dist_table, tile_range, tile_box, tile_dmax);
+                     dist_table ? batch_idx : nullptr, n, dist, dist_table, l.tile_range, l.tile_box, l.tile_dmax);
   hipLaunchKernelGGL(ccl_pairs_kernel, dim3((unsigned)((tiles + CCL_TJ - 1) / CCL_TJ), (unsigned)tiles), dim3(256), 0, stream,
                      points, (int)point_stride, batch_idx,
-                     n, dist, parent, (int)tiles, dist_table, (const int2*)tile_range, (const float4*)tile_box,
-                     (const float*)tile_dmax);
-  hipLaunchKernelGGL(ccl_flatten_kernel, dim3(grid), dim3(256), 0, stream, parent, n);
-  RootIn rin{parent};
-  RootOut rout{rank};
-  int rc = exclusive_scan_u32(rin, rout, n, tile_sums, nullptr, num_components_dev, stream);
+                     n, dist, l.parent, (int)tiles, dist_table, (const int2*)l.tile_range, (const float4*)l.tile_box,
+                     (const float*)l.tile_dmax);
+  hipLaunchKernelGGL(ccl_flatten_kernel, dim3(grid), dim3(256), 0, stream, l.parent, n);
+  RootIn rin{l.parent};
+  RootOut rout{l.rank};
+  int rc = exclusive_scan_u32(rin, rout, n, l.tile_sums, nullptr, num_components_dev, stream);
   if (rc != FSF_OK) return rc;
-  hipLaunchKernelGGL(ccl_label_kernel, dim3(grid), dim3(256), 0, stream, parent, rank, n, labels);
+  hipLaunchKernelGGL(ccl_label_kernel, dim3(grid), dim3(256), 0, stream, l.parent, l.rank, n, labels);
   FSF_LAUNCH_CHECK();
   return FSF_OK;
 }

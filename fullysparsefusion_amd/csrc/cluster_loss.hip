@@ -236,12 +236,20 @@ static int cluster_loss_check(const float* cls_logits, int64_t ld_cls, const flo
 
 using namespace fsf;
 
+struct ClTargetsLayout {
+  int nblk;
+  float *table, *enc;
+  int32_t *box_hit, *partial;
+  ClTargetsLayout(FsfArena& arena, int64_t num_boxes, int64_t n)
+      : nblk(fsf_cdiv(n, CL_BLOCK)), table(arena.take<float>(BOX_WORDS * num_boxes)), enc(arena.take<float>(CL_ENC_WORDS * num_boxes)),
+        box_hit(arena.take<int32_t>(num_boxes)), partial(arena.take<int32_t>(nblk)) {}
+};
+// (one slice: a function in place of a layout struct, taken from a hand-made arena in the entry)
+static double* cluster_loss_layout(FsfArena& arena, int64_t n) { return arena.take<double>(CL_PARTS * (int64_t)fsf_cdiv(n, CL_BLOCK)); }
+
 extern "C" int64_t fsf_cluster_targets_workspace_bytes(int64_t num_boxes, int64_t n) {
   if (num_boxes < 0 || n < 0) return -1;
-  const int64_t m = num_boxes > 0 ? num_boxes : 1;
-  const int64_t nblk = fsf_cdiv(n, CL_BLOCK) > 0 ? fsf_cdiv(n, CL_BLOCK) : 1;
-  return fsf_align_up((int64_t)sizeof(float) * BOX_WORDS * m, 256) + fsf_align_up((int64_t)sizeof(float) * CL_ENC_WORDS * m, 256) +
-         fsf_align_up((int64_t)sizeof(int32_t) * m, 256) + fsf_align_up((int64_t)sizeof(int32_t) * nblk, 256);
+  return fsf_layout_bytes<ClTargetsLayout>(num_boxes, n);
 }
 
 extern "C" int fsf_cluster_targets(const float* cluster_xyz, int64_t n, int64_t xyz_stride, const void* batch_idx, int32_t batch_idx_bytes,
@@ -261,39 +269,34 @@ extern "C" int fsf_cluster_targets(const float* cluster_xyz, int64_t n, int64_t 
     if ((box_cols == 7) != (code_size == 8)) return FSF_ERR_INVALID_ARG;  // the coder appends box columns 7, 8 exactly when they exist
   }
   if (n >= ((int64_t)1 << 24) || num_boxes >= ((int64_t)1 << 24)) return FSF_ERR_UNSUPPORTED;  // (the f32 log scalars stay exact)
-  FsfArena arena(workspace, workspace_bytes);
-  float* table = arena.take<float>(BOX_WORDS * num_boxes);
-  float* enc = arena.take<float>(CL_ENC_WORDS * num_boxes);
-  int32_t* box_hit = arena.take<int32_t>(num_boxes);
-  const int nblk = fsf_cdiv(n, CL_BLOCK);
-  int32_t* partial = arena.take<int32_t>(nblk);
-  if (!arena.ok()) return FSF_ERR_WORKSPACE;
+  FSF_CARVE(ClTargetsLayout, l, workspace, workspace_bytes, num_boxes, n);
   if (num_boxes > 0) {
     hipLaunchKernelGGL(cluster_box_prep_kernel, dim3((unsigned)fsf_cdiv(num_boxes, CL_BLOCK)), dim3(CL_BLOCK), 0, stream, boxes, num_boxes,
-                       box_stride, enlarge_width, table, enc, box_hit);
+                       box_stride, enlarge_width, l.table, l.enc, l.box_hit);
     FSF_LAUNCH_CHECK();
   }
-  if (nblk > 0) {
+  if (l.nblk > 0) {
     if (batch_idx_bytes == 8)
-      hipLaunchKernelGGL(cluster_targets_kernel<int64_t>, dim3((unsigned)nblk), dim3(CL_BLOCK), 0, stream, cluster_xyz, n, xyz_stride,
-                         (const int64_t*)batch_idx, batch_stride, box_ptr, num_samples, boxes, box_stride, box_cols, table, enc, box_labels,
-                         num_classes, code_size, labels, bbox_targets, bbox_weights, assigned, box_hit, partial);
+      hipLaunchKernelGGL(cluster_targets_kernel<int64_t>, dim3((unsigned)l.nblk), dim3(CL_BLOCK), 0, stream, cluster_xyz, n, xyz_stride,
+                         (const int64_t*)batch_idx, batch_stride, box_ptr, num_samples, boxes, box_stride, box_cols, l.table, l.enc, box_labels,
+                         num_classes, code_size, labels, bbox_targets, bbox_weights, assigned, l.box_hit, l.partial);
     else
-      hipLaunchKernelGGL(cluster_targets_kernel<int32_t>, dim3((unsigned)nblk), dim3(CL_BLOCK), 0, stream, cluster_xyz, n, xyz_stride,
-                         (const int32_t*)batch_idx, batch_stride, box_ptr, num_samples, boxes, box_stride, box_cols, table, enc, box_labels,
-                         num_classes, code_size, labels, bbox_targets, bbox_weights, assigned, box_hit, partial);
+      hipLaunchKernelGGL(cluster_targets_kernel<int32_t>, dim3((unsigned)l.nblk), dim3(CL_BLOCK), 0, stream, cluster_xyz, n, xyz_stride,
+                         (const int32_t*)batch_idx, batch_stride, box_ptr, num_samples, boxes, box_stride, box_cols, l.table, l.enc, box_labels,
+                         num_classes, code_size, labels, bbox_targets, bbox_weights, assigned, l.box_hit, l.partial);
     FSF_LAUNCH_CHECK();
   }
-  hipLaunchKernelGGL(cluster_targets_final_kernel, dim3(1), dim3(CL_BLOCK), 0, stream, partial, (int64_t)nblk, box_labels, box_hit, num_boxes,
-                     n, nblk > 0, stats);
+  hipLaunchKernelGGL(cluster_targets_final_kernel, dim3(1), dim3(CL_BLOCK), 0, stream, l.partial, (int64_t)l.nblk, box_labels, l.box_hit, num_boxes,
+                     n, l.nblk > 0, stats);
   FSF_LAUNCH_CHECK();
   return FSF_OK;
 }
 
 extern "C" int64_t fsf_cluster_loss_workspace_bytes(int64_t n) {
   if (n < 0) return -1;
-  const int64_t nblk = fsf_cdiv(n, CL_BLOCK);
-  return fsf_align_up((int64_t)sizeof(double) * CL_PARTS * (nblk > 0 ? nblk : 1), 256);
+  FsfArena arena = FsfArena::measure();
+  cluster_loss_layout(arena, n);
+  return arena.used;
 }
 
 extern "C" int fsf_cluster_loss_forward(const float* cls_logits, int64_t ld_cls, const float* reg_preds, int64_t ld_reg, int64_t n,
@@ -308,7 +311,7 @@ extern "C" int fsf_cluster_loss_forward(const float* cls_logits, int64_t ld_cls,
   if (!losses || !counts || (with_vel && code_size != 10)) return FSF_ERR_INVALID_ARG;
   FsfArena arena(workspace, workspace_bytes);
   const int nblk = fsf_cdiv(n, CL_BLOCK);
-  double* partials = arena.take<double>(CL_PARTS * (int64_t)nblk);
+  double* partials = cluster_loss_layout(arena, n);
   if (!arena.ok()) return FSF_ERR_WORKSPACE;
   if (nblk > 0) {
     hipLaunchKernelGGL(cluster_loss_partials_kernel, dim3((unsigned)nblk), dim3(CL_BLOCK), 0, stream, cls_logits, ld_cls, reg_preds, ld_reg,

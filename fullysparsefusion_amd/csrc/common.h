@@ -111,25 +111,54 @@ static inline int fsf_stream_grid(int64_t work_items, int block) {
   return (int)g;
 }
 
-// Bump allocator over the caller's workspace (256-byte aligned slices).
+// Bump allocator over the caller's workspace (256-byte aligned slices).  An entry point's layout is ONE function that takes its slices
+// from an arena; FsfArena::measure() runs the same function with no memory behind it — every take returns nullptr and advances `used`
+// as a real arena would — so the entry's *_workspace_bytes query is `used` after the layout and cannot drift from the carve.
 struct FsfArena {
   char* base;
   int64_t size;
   int64_t used;
-  __host__ FsfArena(void* p, int64_t n) : base((char*)p), size(n), used(0) {}
-  template <typename T>
-  __host__ T* take(int64_t count) {
-    int64_t bytes = fsf_align_up((int64_t)sizeof(T) * (count > 0 ? count : 1), 256);
+  bool measuring;
+  __host__ FsfArena(void* p, int64_t n) : base((char*)p), size(n), used(0), measuring(false) {}
+  __host__ static FsfArena measure() {
+    FsfArena a(nullptr, 0);
+    a.measuring = true;
+    return a;
+  }
+  __host__ void* take_bytes(int64_t n) {
+    const int64_t bytes = fsf_align_up(n > 0 ? n : 1, 256);
+    if (measuring) {
+      used += bytes;
+      return nullptr;
+    }
     if (base == nullptr || used + bytes > size) {
       used = size + 1;  // poison
       return nullptr;
     }
-    T* r = (T*)(base + used);
+    void* r = base + used;
     used += bytes;
     return r;
   }
-  __host__ bool ok() const { return used <= size; }
+  template <typename T>
+  __host__ T* take(int64_t count) {
+    return (T*)take_bytes((int64_t)sizeof(T) * (count > 0 ? count : 1));
+  }
+  __host__ int64_t offset() const { return used; }  // of the next slice: spans of consecutive slices without pointer arithmetic
+  __host__ bool ok() const { return measuring || used <= size; }
 };
+// an entry point's carve: `const Layout name(arena over the caller's workspace, args...)`, or FSF_ERR_WORKSPACE when it does not fit.
+// Three statements ending in a bare `if (...) return`: a statement of its own in the entry's body, never the body of an unbraced
+// if / else; it also declares `name_arena` in the caller's scope.
+#define FSF_CARVE(Layout, name, workspace, bytes, ...) \
+  FsfArena name##_arena((workspace), (bytes));         \
+  const Layout name(name##_arena, __VA_ARGS__);        \
+  if (!name##_arena.ok()) return FSF_ERR_WORKSPACE
+// what a size query answers: the bytes `Layout(arena, args...)` takes
+template <class Layout, class... Args>
+static inline int64_t fsf_layout_bytes(Args... args) {
+  FsfArena ar = FsfArena::measure();
+  return ((void)Layout(ar, args...), ar.used);
+}
 
 __device__ __forceinline__ int fsf_lane() { return threadIdx.x & 63; }
 

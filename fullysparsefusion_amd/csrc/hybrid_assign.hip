@@ -331,14 +331,19 @@ extern "C" int fsf_gt_boxes_2d(const float* boxes, int64_t num_boxes, int64_t bo
   return FSF_OK;
 }
 
+struct HyLayout {
+  int nblk;
+  float *table, *enc;
+  int32_t *box_hit, *partial;
+  float* gt_max;
+  HyLayout(FsfArena& arena, int64_t num_boxes, int64_t pairs, int64_t n)
+      : nblk(fsf_cdiv(n, HY_BLOCK)), table(arena.take<float>(BOX_WORDS * num_boxes)), enc(arena.take<float>(CL_ENC_WORDS * num_boxes)),
+        box_hit(arena.take<int32_t>(num_boxes)), partial(arena.take<int32_t>(nblk)), gt_max(arena.take<float>(pairs)) {}
+};
+
 extern "C" int64_t fsf_hybrid_assign_workspace_bytes(int64_t num_boxes, int64_t num_boxes_2d, int32_t ncam, int64_t n) {
   if (num_boxes < 0 || num_boxes_2d < 0 || ncam < 1 || n < 0) return -1;
-  const int64_t m = num_boxes > 0 ? num_boxes : 1;
-  const int64_t pairs = num_boxes_2d * ncam > 0 ? num_boxes_2d * ncam : 1;
-  const int64_t nblk = fsf_cdiv(n, HY_BLOCK) > 0 ? fsf_cdiv(n, HY_BLOCK) : 1;
-  return fsf_align_up((int64_t)sizeof(float) * BOX_WORDS * m, 256) + fsf_align_up((int64_t)sizeof(float) * CL_ENC_WORDS * m, 256) +
-         fsf_align_up((int64_t)sizeof(int32_t) * m, 256) + fsf_align_up((int64_t)sizeof(int32_t) * nblk, 256) +
-         fsf_align_up((int64_t)sizeof(float) * pairs, 256);
+  return fsf_layout_bytes<HyLayout>(num_boxes, num_boxes_2d * ncam, n);
 }
 
 // K37b and K38 share everything: `ext` selects the per-query kernel with the distance step and the source output.
@@ -368,18 +373,11 @@ static int hybrid_assign_run(const float* cluster_xyz, int64_t n, int64_t xyz_st
   if (n >= ((int64_t)1 << 24) || num_boxes >= ((int64_t)1 << 24) || num_boxes_2d >= ((int64_t)1 << 24) ||
       ((uintptr_t)boxes_2d % 16) != 0)
     return FSF_ERR_UNSUPPORTED;
-  FsfArena arena(workspace, workspace_bytes);
-  float* table = arena.take<float>(BOX_WORDS * num_boxes);
-  float* enc = arena.take<float>(CL_ENC_WORDS * num_boxes);
-  int32_t* box_hit = arena.take<int32_t>(num_boxes);
-  const int nblk = fsf_cdiv(n, HY_BLOCK);
-  int32_t* partial = arena.take<int32_t>(nblk);
   const int64_t pairs = num_boxes_2d * ncam;
-  float* gt_max = arena.take<float>(pairs);
-  if (!arena.ok()) return FSF_ERR_WORKSPACE;
+  FSF_CARVE(HyLayout, l, workspace, workspace_bytes, num_boxes, pairs, n);
   if (num_boxes > 0) {
     hipLaunchKernelGGL(hybrid_box_prep_kernel, dim3((unsigned)fsf_cdiv(num_boxes, HY_BLOCK)), dim3(HY_BLOCK), 0, stream, boxes, num_boxes,
-                       box_stride, extra_height, table, enc, box_hit);
+                       box_stride, extra_height, l.table, l.enc, l.box_hit);
     FSF_LAUNCH_CHECK();
   }
   const bool wide = batch_idx_bytes == 8;
@@ -387,18 +385,18 @@ static int hybrid_assign_run(const float* cluster_xyz, int64_t n, int64_t xyz_st
     const dim3 grid((unsigned)fsf_cdiv(pairs, HY_BLOCK / FSF_WAVE));
     if (wide)
       hipLaunchKernelGGL(hybrid_gt_max_kernel<int64_t>, grid, dim3(HY_BLOCK), 0, stream, preds_2d, n, preds_stride,
-                         (const int64_t*)batch_idx, batch_stride, box_ptr_2d, num_samples, boxes_2d, keep_2d, pairs, ncam, gt_max);
+                         (const int64_t*)batch_idx, batch_stride, box_ptr_2d, num_samples, boxes_2d, keep_2d, pairs, ncam, l.gt_max);
     else
       hipLaunchKernelGGL(hybrid_gt_max_kernel<int32_t>, grid, dim3(HY_BLOCK), 0, stream, preds_2d, n, preds_stride,
-                         (const int32_t*)batch_idx, batch_stride, box_ptr_2d, num_samples, boxes_2d, keep_2d, pairs, ncam, gt_max);
+                         (const int32_t*)batch_idx, batch_stride, box_ptr_2d, num_samples, boxes_2d, keep_2d, pairs, ncam, l.gt_max);
     FSF_LAUNCH_CHECK();
   }
-  if (nblk > 0) {
+  if (l.nblk > 0) {
 #define FSF_HY_LAUNCH(BT, EXT)                                                                                                          \
-  hipLaunchKernelGGL((hybrid_assign_kernel<BT, EXT>), dim3((unsigned)nblk), dim3(HY_BLOCK), 0, stream, cluster_xyz, n, xyz_stride,     \
-                     (const BT*)batch_idx, batch_stride, preds_2d, preds_stride, box_ptr_2d, boxes_2d, keep_2d, gt_max, num_boxes_2d,  \
-                     ncam, box_ptr, num_samples, boxes, num_boxes, box_stride, box_cols, table, enc, box_labels, num_classes,          \
-                     code_size, pos_iou_thr, min_pos_iou, labels, bbox_targets, bbox_weights, assigned, box_hit, partial,              \
+  hipLaunchKernelGGL((hybrid_assign_kernel<BT, EXT>), dim3((unsigned)l.nblk), dim3(HY_BLOCK), 0, stream, cluster_xyz, n, xyz_stride,     \
+                     (const BT*)batch_idx, batch_stride, preds_2d, preds_stride, box_ptr_2d, boxes_2d, keep_2d, l.gt_max, num_boxes_2d,  \
+                     ncam, box_ptr, num_samples, boxes, num_boxes, box_stride, box_cols, l.table, l.enc, box_labels, num_classes,          \
+                     code_size, pos_iou_thr, min_pos_iou, labels, bbox_targets, bbox_weights, assigned, l.box_hit, l.partial,              \
                      old_cls_logits, logits_stride, class_max_dist, source)
     if (wide && ext) FSF_HY_LAUNCH(int64_t, true);
     else if (wide) FSF_HY_LAUNCH(int64_t, false);
@@ -407,8 +405,8 @@ static int hybrid_assign_run(const float* cluster_xyz, int64_t n, int64_t xyz_st
 #undef FSF_HY_LAUNCH
     FSF_LAUNCH_CHECK();
   }
-  hipLaunchKernelGGL(hybrid_assign_final_kernel, dim3(1), dim3(HY_BLOCK), 0, stream, partial, (int64_t)nblk, box_labels, box_hit, num_boxes,
-                     n, nblk > 0, stats);
+  hipLaunchKernelGGL(hybrid_assign_final_kernel, dim3(1), dim3(HY_BLOCK), 0, stream, l.partial, (int64_t)l.nblk, box_labels, l.box_hit, num_boxes,
+                     n, l.nblk > 0, stats);
   FSF_LAUNCH_CHECK();
   return FSF_OK;
 }

@@ -12,48 +12,91 @@
 //
 // Memory: the caller hands over ONE arena (fsf_lidar_cluster_frontend_arena_bytes(m, ng, point_cols): the worst case, every (group, point)
 // pair surviving); intermediates and results are bump-allocated inside it in the order below, and the results' byte offsets + row counts
-// come back in `out` (host i64 [FSF_LCF_OUT_WORDS]).  Nothing is allocated or freed here.
+// come back in `out` (host i64 [FSF_LCF_OUT_WORDS]).  Nothing is allocated or freed here.  The size is computed by running the entry's
+// own stage layouts (LcfPairs ... LcfCentroids) on a measuring arena with every count at its worst case.
 #include "common.h"
 
 namespace {
 
-struct Bump {
-  char* base;
-  int64_t size, used;
-  bool dry;
-  template <typename T>
-  T* take(int64_t count) {
-    const int64_t bytes = fsf_align_up((int64_t)sizeof(T) * (count > 0 ? count : 1), 256);
-    const int64_t at = used;
-    used += bytes;
-    if (dry) return nullptr;
-    if (used > size) return nullptr;
-    return reinterpret_cast<T*>(base + at);
-  }
-  void* take_bytes(int64_t bytes) { return take<char>(bytes); }
-  int64_t off(const void* p) const { return p ? (int64_t)((const char*)p - base) : -1; }
+// One layout per stage: a stage ends where the device tells the host a count (P pairs, K voxel keys, K' kept keys and V kept pairs,
+// C clusters) that sizes the next one.  The entry point runs them in this order with the counts it reads back, the size query with
+// cap = max(m, 1) * ng for every count.  The scratch of a nested entry point is one slice of that entry's own size query.
+struct LcfWs {
+  int64_t bytes;
+  void* p;
+  LcfWs(FsfArena& a, int64_t n) : bytes(n), p(a.take_bytes(n)) {}
+};
+// the outputs and scratch of one fsf_unique_rows over n rows of k columns
+struct LcfUnique {
+  int64_t *rows, *inv, *cnt;
+  int32_t *order, *offs;
+  int64_t* m_dev;
+  LcfWs ws;
+  LcfUnique(FsfArena& a, int64_t n, int32_t k)
+      : rows(a.take<int64_t>(n * k)), inv(a.take<int64_t>(n)), cnt(a.take<int64_t>(n)), order(a.take<int32_t>(n)),
+        offs(a.take<int32_t>(n + 1)), m_dev(a.take<int64_t>(1)), ws(a, fsf_unique_rows_workspace_bytes(n, k)) {}
+};
+// (group, point) pairs of the grouped sampling (:826-838)
+struct LcfPairs {
+  int64_t *g_ids, *p_ids;
+  LcfWs ws;
+  LcfPairs(FsfArena& a, int64_t m, int32_t ng)
+      : g_ids(a.take<int64_t>(m * ng)), p_ids(a.take<int64_t>(m * ng)), ws(a, fsf_group_pairs_workspace_bytes(m, ng)) {}
+};
+// vote centres and cluster-voxel keys of every pair (:840-865, :945-950); one unique over the keys of all groups (:31-35 per group upstream)
+struct LcfVotes {
+  float* centers;
+  int64_t *keys, *b_pts;
+  LcfUnique uq;
+  LcfVotes(FsfArena& a, int64_t P) : centers(a.take<float>(P * 3)), keys(a.take<int64_t>(P * 4)), b_pts(a.take<int64_t>(P)), uq(a, P, 4) {}
+};
+// the density filter (:951-956): surviving keys / pairs
+struct LcfSurvival {
+  int64_t* k_idx;
+  int32_t* k_group;
+  int64_t *v_idx, *vox_inv;
+  LcfWs ws;
+  LcfSurvival(FsfArena& a, int64_t K, int64_t P)
+      : k_idx(a.take<int64_t>(K)), k_group(a.take<int32_t>(K)), v_idx(a.take<int64_t>(P)), vox_inv(a.take<int64_t>(P)),
+        ws(a, fsf_cluster_key_survival_workspace_bytes(K, P)) {}
+};
+// voxel centroids of the votes (every key's, then the survivors' rows), the survivors of the per-pair tensors, connected components of
+// the kept voxels per group (:45-82), cluster ids of the pairs (:971-977), the pairs' point rows, and the SIR stack's one unique over
+// (group, sample, cluster id) (models/backbones/sir.py:68)
+struct LcfClusters {
+  float *all_means, *vox_centers;
+  int64_t *g_out, *p_out, *b_out;
+  float* centers_out;
+  int32_t* labels;
+  LcfWs cc_ws, id_ws;
+  int64_t* pci;
+  float* pts_out;
+  LcfUnique uq;
+  LcfClusters(FsfArena& a, int64_t K, int64_t Kk, int64_t V, int32_t point_cols)
+      : all_means(a.take<float>(K * 3)), vox_centers(a.take<float>(Kk * 3)), g_out(a.take<int64_t>(V)), p_out(a.take<int64_t>(V)),
+        b_out(a.take<int64_t>(V)), centers_out(a.take<float>(V * 3)), labels(a.take<int32_t>(Kk)),
+        cc_ws(a, fsf_connected_components_workspace_bytes(Kk)), id_ws(a, 256), pci(a.take<int64_t>(V * 3)),
+        pts_out(a.take<float>(V * (int64_t)point_cols)), uq(a, V, 3) {}
+};
+// the cluster centroids (:458-474)
+struct LcfCentroids {
+  float* cluster_xyz;
+  LcfWs ws;
+  LcfCentroids(FsfArena& a, int64_t V, int64_t C) : cluster_xyz(a.take<float>(C * 3)), ws(a, fsf_segment_reduce_workspace_bytes(V, C, 3)) {}
 };
 
 }  // namespace
 
 extern "C" int64_t fsf_lidar_cluster_frontend_arena_bytes(int64_t m, int32_t ng, int32_t point_cols) {
   if (m < 0 || ng < 1 || point_cols < 3) return 0;
-  const int64_t cap = (m > 0 ? m : 1) * ng;  // every pair survives every filter: P = K = K' = V = C = cap
-  int64_t b = 0;
-  auto add = [&](int64_t bytes) { b += fsf_align_up(bytes > 0 ? bytes : 1, 256); };
-  add(cap * 8); add(cap * 8); add(fsf_group_pairs_workspace_bytes(m, ng));                      // g_ids, p_ids, pair scratch
-  add(cap * 12); add(cap * 32); add(cap * 8);                                                    // centers, keys, b_pts
-  add(cap * 32); add(cap * 8); add(cap * 8); add(cap * 4); add((cap + 1) * 4); add(8);           // unique 1
-  add(fsf_unique_rows_workspace_bytes(cap, 4));
-  add(cap * 8); add(cap * 4); add(cap * 8); add(cap * 8); add(fsf_cluster_key_survival_workspace_bytes(cap, cap));
-  add(cap * 12); add(cap * 12);                                                                  // all means, kept means
-  add(cap * 8); add(cap * 8); add(cap * 8); add(cap * 12);                                       // compacted pairs
-  add(cap * 4); add(fsf_connected_components_workspace_bytes(cap)); add(256);                    // labels, CCL scratch, id scratch
-  add(cap * 24); add(cap * (int64_t)point_cols * 4);                                             // pts_cluster_inds, points
-  add(cap * 24); add(cap * 8); add(cap * 8); add(cap * 4); add((cap + 1) * 4); add(8);           // unique 2
-  add(fsf_unique_rows_workspace_bytes(cap, 3));
-  add(cap * 12); add(fsf_segment_reduce_workspace_bytes(cap, cap, 3));                           // cluster centroids
-  return b + 4096;
+  const int64_t m1 = m > 0 ? m : 1, cap = m1 * ng;  // every pair survives every filter: P = K = K' = V = C = cap
+  FsfArena a = FsfArena::measure();
+  LcfPairs(a, m1, ng);
+  LcfVotes(a, cap);
+  LcfSurvival(a, cap, cap);
+  LcfClusters(a, cap, cap, cap, point_cols);
+  LcfCentroids(a, cap, cap);
+  return a.used;
 }
 
 // out (host): see FSF_LCF_* in include/fsf_hip.h
@@ -66,114 +109,74 @@ extern "C" int fsf_lidar_cluster_frontend(const float* scores, int64_t m, int32_
   if (m < 1 || ng < 1 || ng > 32 || !scores || !thresh || !group_class_masks || !logits || !offsets || !points || !group_voxel_size ||
       !range_min || !key_min || !key_max || !dist_table || !arena || !out || point_cols < 3 || point_stride < point_cols)
     return FSF_ERR_INVALID_ARG;
+  // (up front, against the worst case: the stages below launch before the last of them takes its slices)
   if (arena_bytes < fsf_lidar_cluster_frontend_arena_bytes(m, ng, point_cols) || ((uintptr_t)arena & 255)) return FSF_ERR_WORKSPACE;
   for (int i = 0; i < FSF_LCF_OUT_WORDS; ++i) out[i] = 0;
-  Bump a{(char*)arena, arena_bytes, 0, false};
+  FsfArena a(arena, arena_bytes);
   const int64_t cap = m * ng;
   int rc;
 
-  // ---- (group, point) pairs of the grouped sampling (:826-838)
-  int64_t* g_ids = a.take<int64_t>(cap);
-  int64_t* p_ids = a.take<int64_t>(cap);
-  const int64_t gp_ws_bytes = fsf_group_pairs_workspace_bytes(m, ng);
-  void* gp_ws = a.take_bytes(gp_ws_bytes);
+  const LcfPairs pr(a, m, ng);
   int64_t P = 0;
-  rc = fsf_group_pairs(scores, m, ng, score_stride, thresh, 1, group_class_masks, num_classes, g_ids, p_ids, cap, &P, gp_ws, gp_ws_bytes, stream);
+  rc = fsf_group_pairs(scores, m, ng, score_stride, thresh, 1, group_class_masks, num_classes, pr.g_ids, pr.p_ids, cap, &P, pr.ws.p, pr.ws.bytes,
+                       stream);
   if (rc != FSF_OK) return rc;
   if (P < 1) return FSF_ERR_INVALID_ARG;  // (keep_one leaves at least one pair per group)
 
-  // ---- vote centres and cluster-voxel keys of every pair (:840-865, :945-950)
-  float* centers = a.take<float>(P * 3);
-  int64_t* keys = a.take<int64_t>(P * 4);
-  int64_t* b_pts = a.take<int64_t>(P);
-  rc = fsf_vote_centers_keys(logits, logit_stride, offsets, offset_stride, points, point_stride, batch_idx, g_ids, p_ids, P, num_classes, ng,
-                             group_class_masks, group_voxel_size, range_min, 1, centers, keys, b_pts, stream);
+  const LcfVotes vt(a, P);
+  rc = fsf_vote_centers_keys(logits, logit_stride, offsets, offset_stride, points, point_stride, batch_idx, pr.g_ids, pr.p_ids, P, num_classes,
+                             ng, group_class_masks, group_voxel_size, range_min, 1, vt.centers, vt.keys, vt.b_pts, stream);
   if (rc != FSF_OK) return rc;
-
-  // ---- one unique over the keys of all groups (:31-35 per group upstream)
-  int64_t* new_keys = a.take<int64_t>(P * 4);
-  int64_t* inv = a.take<int64_t>(P);
-  int64_t* cnt = a.take<int64_t>(P);
-  int32_t* order = a.take<int32_t>(P);
-  int32_t* offs = a.take<int32_t>(P + 1);
-  int64_t* m_dev = a.take<int64_t>(1);
-  const int64_t uq_ws_bytes = fsf_unique_rows_workspace_bytes(P, 4);
-  void* uq_ws = a.take_bytes(uq_ws_bytes);
+  const LcfUnique& u1 = vt.uq;
   int64_t K = 0;
-  rc = fsf_unique_rows(keys, P, 4, key_min, key_max, new_keys, inv, cnt, order, offs, m_dev, &K, uq_ws, uq_ws_bytes, stream);
+  rc = fsf_unique_rows(vt.keys, P, 4, key_min, key_max, u1.rows, u1.inv, u1.cnt, u1.order, u1.offs, u1.m_dev, &K, u1.ws.p, u1.ws.bytes, stream);
   if (rc == FSF_ERR_KEY_RANGE)  // a vote outside the caller's bounds: the data-dependent range pass (as sst_ops.unique_with_plan does)
-    rc = fsf_unique_rows(keys, P, 4, nullptr, nullptr, new_keys, inv, cnt, order, offs, m_dev, &K, uq_ws, uq_ws_bytes, stream);
+    rc = fsf_unique_rows(vt.keys, P, 4, nullptr, nullptr, u1.rows, u1.inv, u1.cnt, u1.order, u1.offs, u1.m_dev, &K, u1.ws.p, u1.ws.bytes, stream);
   if (rc != FSF_OK) return rc;
 
-  // ---- the density filter (:951-956): surviving keys / pairs
-  int64_t* k_idx = a.take<int64_t>(K);
-  int32_t* k_group = a.take<int32_t>(K);
-  int64_t* v_idx = a.take<int64_t>(P);
-  int64_t* vox_inv = a.take<int64_t>(P);
-  const int64_t ks_ws_bytes = fsf_cluster_key_survival_workspace_bytes(K, P);
-  void* ks_ws = a.take_bytes(ks_ws_bytes);
+  const LcfSurvival sv(a, K, P);
   int64_t counts[2] = {0, 0};
-  rc = fsf_cluster_key_survival(new_keys, 4, cnt, K, inv, P, 1, min_points, ng, k_idx, k_group, v_idx, vox_inv, counts, ks_ws, ks_ws_bytes, stream);
+  rc = fsf_cluster_key_survival(u1.rows, 4, u1.cnt, K, u1.inv, P, 1, min_points, ng, sv.k_idx, sv.k_group, sv.v_idx, sv.vox_inv, counts, sv.ws.p,
+                                sv.ws.bytes, stream);
   if (rc != FSF_OK) return rc;
   const int64_t Kk = counts[0], V = counts[1];
 
-  // ---- voxel centroids of the votes (every key's, then the survivors' rows) and the survivors of the per-pair tensors
-  float* all_means = a.take<float>(K * 3);
-  float* vox_centers = a.take<float>(Kk * 3);
+  const LcfClusters cl(a, K, Kk, V, point_cols);
   {
-    const float* fp[1] = {centers};
+    const float* fp[1] = {vt.centers};
     const int64_t st[1] = {3};
     const int32_t cs[1] = {3};
-    float* op[1] = {all_means};
-    rc = fsf_segment_reduce_short(fp, st, cs, 1, P, order, offs, K, 1 /* mean */, op, nullptr, stream);
+    float* op[1] = {cl.all_means};
+    rc = fsf_segment_reduce_short(fp, st, cs, 1, P, u1.order, u1.offs, K, 1 /* mean */, op, nullptr, stream);
     if (rc != FSF_OK) return rc;
   }
-  int64_t* g_out = a.take<int64_t>(V);
-  int64_t* p_out = a.take<int64_t>(V);
-  int64_t* b_out = a.take<int64_t>(V);
-  float* centers_out = a.take<float>(V * 3);
-  rc = fsf_compact_pairs(all_means, 3, k_idx, Kk, vox_centers, g_ids, p_ids, b_pts, centers, v_idx, V, g_out, p_out, b_out, centers_out, stream);
+  rc = fsf_compact_pairs(cl.all_means, 3, sv.k_idx, Kk, cl.vox_centers, pr.g_ids, pr.p_ids, vt.b_pts, vt.centers, sv.v_idx, V, cl.g_out, cl.p_out,
+                         cl.b_out, cl.centers_out, stream);
   if (rc != FSF_OK) return rc;
-
-  // ---- connected components of the kept voxels per group (:45-82), cluster ids of the pairs (:971-977), the pairs' point rows
-  int32_t* labels = a.take<int32_t>(Kk);
-  const int64_t cc_ws_bytes = fsf_connected_components_workspace_bytes(Kk);
-  void* cc_ws = a.take_bytes(cc_ws_bytes);
-  void* id_ws = a.take_bytes(256);
-  rc = fsf_connected_components_grouped(vox_centers, Kk, 3, k_group, dist_table, ng, labels, nullptr, cc_ws, cc_ws_bytes, stream);
+  rc = fsf_connected_components_grouped(cl.vox_centers, Kk, 3, sv.k_group, dist_table, ng, cl.labels, nullptr, cl.cc_ws.p, cl.cc_ws.bytes, stream);
   if (rc != FSF_OK) return rc;
-  int64_t* pci = a.take<int64_t>(V * 3);
-  rc = fsf_cluster_point_ids(labels, k_group, Kk, vox_inv, g_out, b_out, V, ng, pci, id_ws, 256, stream);
+  rc = fsf_cluster_point_ids(cl.labels, sv.k_group, Kk, sv.vox_inv, cl.g_out, cl.b_out, V, ng, cl.pci, cl.id_ws.p, cl.id_ws.bytes, stream);
   if (rc != FSF_OK) return rc;
-  float* pts_out = a.take<float>(V * (int64_t)point_cols);
-  rc = fsf_gather_rows_strided(points, point_stride, m, point_cols, p_out, V, pts_out, point_cols, stream);
+  rc = fsf_gather_rows_strided(points, point_stride, m, point_cols, cl.p_out, V, cl.pts_out, point_cols, stream);
   if (rc != FSF_OK) return rc;
-
-  // ---- the SIR stack's one unique over (group, sample, cluster id) (models/backbones/sir.py:68) and the cluster centroids (:458-474)
-  int64_t* new_coors = a.take<int64_t>(V * 3);
-  int64_t* inv2 = a.take<int64_t>(V);
-  int64_t* cnt2 = a.take<int64_t>(V);
-  int32_t* order2 = a.take<int32_t>(V);
-  int32_t* offs2 = a.take<int32_t>(V + 1);
-  int64_t* m_dev2 = a.take<int64_t>(1);
-  const int64_t uq2_ws_bytes = fsf_unique_rows_workspace_bytes(V, 3);
-  void* uq2_ws = a.take_bytes(uq2_ws_bytes);
+  const LcfUnique& u2 = cl.uq;
   const int64_t c_min[3] = {0, 0, 0}, c_max[3] = {ng - 1, 0, Kk > 0 ? Kk - 1 : 0};
   int64_t C = 0;
-  rc = fsf_unique_rows(pci, V, 3, c_min, c_max, new_coors, inv2, cnt2, order2, offs2, m_dev2, &C, uq2_ws, uq2_ws_bytes, stream);
-  if (rc == FSF_ERR_KEY_RANGE) rc = fsf_unique_rows(pci, V, 3, nullptr, nullptr, new_coors, inv2, cnt2, order2, offs2, m_dev2, &C, uq2_ws, uq2_ws_bytes, stream);
-  if (rc != FSF_OK) return rc;
-  float* cluster_xyz = a.take<float>(C * 3);
-  const int64_t sr_ws_bytes = fsf_segment_reduce_workspace_bytes(V, C, 3);
-  void* sr_ws = a.take_bytes(sr_ws_bytes);
-  if (a.used > a.size) return FSF_ERR_WORKSPACE;
-  rc = fsf_segment_reduce(centers_out, 3, V, 3, order2, inv2, offs2, C, 1 /* mean */, cluster_xyz, nullptr, sr_ws, sr_ws_bytes, stream);
+  rc = fsf_unique_rows(cl.pci, V, 3, c_min, c_max, u2.rows, u2.inv, u2.cnt, u2.order, u2.offs, u2.m_dev, &C, u2.ws.p, u2.ws.bytes, stream);
+  if (rc == FSF_ERR_KEY_RANGE)
+    rc = fsf_unique_rows(cl.pci, V, 3, nullptr, nullptr, u2.rows, u2.inv, u2.cnt, u2.order, u2.offs, u2.m_dev, &C, u2.ws.p, u2.ws.bytes, stream);
   if (rc != FSF_OK) return rc;
 
+  const LcfCentroids ce(a, V, C);
+  if (!a.ok()) return FSF_ERR_WORKSPACE;
+  rc = fsf_segment_reduce(cl.centers_out, 3, V, 3, u2.order, u2.inv, u2.offs, C, 1 /* mean */, ce.cluster_xyz, nullptr, ce.ws.p, ce.ws.bytes, stream);
+  if (rc != FSF_OK) return rc;
+
+  auto off = [&](const void* p) { return (int64_t)((const char*)p - (const char*)arena); };  // (every slice was taken: a.ok())
   out[FSF_LCF_PAIRS] = P; out[FSF_LCF_KEYS] = K; out[FSF_LCF_KEPT_KEYS] = Kk; out[FSF_LCF_ROWS] = V; out[FSF_LCF_CLUSTERS] = C;
-  out[FSF_LCF_OFF_P_IDS] = a.off(p_out); out[FSF_LCF_OFF_CENTERS] = a.off(centers_out); out[FSF_LCF_OFF_CLUSTER_INDS] = a.off(pci);
-  out[FSF_LCF_OFF_POINTS] = a.off(pts_out); out[FSF_LCF_OFF_NEW_COORS] = a.off(new_coors); out[FSF_LCF_OFF_INV] = a.off(inv2);
-  out[FSF_LCF_OFF_CNT] = a.off(cnt2); out[FSF_LCF_OFF_ORDER] = a.off(order2); out[FSF_LCF_OFF_SEG_OFFSETS] = a.off(offs2);
-  out[FSF_LCF_OFF_CLUSTER_XYZ] = a.off(cluster_xyz);
+  out[FSF_LCF_OFF_P_IDS] = off(cl.p_out); out[FSF_LCF_OFF_CENTERS] = off(cl.centers_out); out[FSF_LCF_OFF_CLUSTER_INDS] = off(cl.pci);
+  out[FSF_LCF_OFF_POINTS] = off(cl.pts_out); out[FSF_LCF_OFF_NEW_COORS] = off(u2.rows); out[FSF_LCF_OFF_INV] = off(u2.inv);
+  out[FSF_LCF_OFF_CNT] = off(u2.cnt); out[FSF_LCF_OFF_ORDER] = off(u2.order); out[FSF_LCF_OFF_SEG_OFFSETS] = off(u2.offs);
+  out[FSF_LCF_OFF_CLUSTER_XYZ] = off(ce.cluster_xyz);
   return FSF_OK;
 }

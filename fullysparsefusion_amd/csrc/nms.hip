@@ -383,29 +383,29 @@ __global__ void __launch_bounds__(256) nms_build_kernel(NmsBuildArgs a) {
 
 using namespace fsf;
 
-static int64_t nms_bins_bytes(int64_t n) {
-  if (n < NMS_BIN_MIN) return 0;
-  return fsf_align_up((int64_t)(2 * NMS_GRID * NMS_GRID + 1) * 4, 256) + 4 * fsf_align_up(n * 4, 256) + 256;
+// the cell counters / lists of the binned mask path: nothing below NMS_BIN_MIN boxes
+static NmsBins nms_bins_layout(FsfArena& arena, int64_t n) {
+  NmsBins b{};
+  if (n < NMS_BIN_MIN) return b;
+  int32_t* cells = arena.take<int32_t>(2 * NMS_GRID * NMS_GRID + 1);
+  b.cell_cnt = cells;
+  b.cell_start = cells ? cells + NMS_GRID * NMS_GRID : nullptr;
+  b.box_cell = arena.take<int32_t>(n);
+  b.box_slot = arena.take<int32_t>(n);
+  b.cell_list = arena.take<int32_t>(n);
+  b.big_list = arena.take<int32_t>(n);
+  b.nbig = arena.take<int32_t>(1);
+  return b;
 }
 
-// pair bits of all boxes into a.mask / a.rowsum (rowsum must be zero on entry); `prezeroed`: the caller has cleared a.mask and everything
-// this function takes from the arena (one memset over the lot instead of three here)
-static int nms_launch_mask(const NmsArgs& a, FsfArena& arena, hipStream_t stream, bool prezeroed = false) {
+// pair bits of all boxes into a.mask / a.rowsum (rowsum must be zero on entry); `prezeroed`: the caller has cleared a.mask and all of
+// `b` (one memset over the lot instead of three here)
+static int nms_launch_mask(const NmsArgs& a, const NmsBins& b, hipStream_t stream, bool prezeroed = false) {
   if (a.n < NMS_BIN_MIN) {
     // words below the diagonal are never written by the mask kernel and never read by the scan / build (w starts at i / 64)
     hipLaunchKernelGGL(nms_mask_kernel, dim3((unsigned)a.words, (unsigned)a.words), dim3(64), 0, stream, a);
     return FSF_OK;
   }
-  NmsBins b{};
-  int32_t* cells = arena.take<int32_t>(2 * NMS_GRID * NMS_GRID + 1);
-  b.cell_cnt = cells;
-  b.cell_start = cells + NMS_GRID * NMS_GRID;
-  b.box_cell = arena.take<int32_t>(a.n);
-  b.box_slot = arena.take<int32_t>(a.n);
-  b.cell_list = arena.take<int32_t>(a.n);
-  b.big_list = arena.take<int32_t>(a.n);
-  b.nbig = arena.take<int32_t>(1);
-  if (!arena.ok()) return FSF_ERR_WORKSPACE;
   if (!prezeroed) {
     FSF_HIP_TRY(hipMemsetAsync(a.mask, 0, (size_t)a.n * a.words * 8, stream));
     FSF_HIP_TRY(hipMemsetAsync(b.cell_cnt, 0, sizeof(int32_t) * NMS_GRID * NMS_GRID, stream));
@@ -420,12 +420,18 @@ static int nms_launch_mask(const NmsArgs& a, FsfArena& arena, hipStream_t stream
   return FSF_OK;
 }
 
-extern "C" int64_t fsf_nms_bev_workspace_bytes(int64_t n) {
-  const int64_t words = (n + 63) / 64, sum_words = (words + 63) / 64;
-  const int64_t n1 = n > 0 ? n : 1;
-  return fsf_align_up(n1 * (words > 0 ? words : 1) * 8, 256) + fsf_align_up(n1 * (sum_words > 0 ? sum_words : 1) * 8, 256) + 512 +
-         nms_bins_bytes(n);
-}
+struct NmsLayout {
+  int64_t words, sum_words;
+  uint64_t *mask, *rowsum;
+  int64_t* tmp;
+  NmsBins bins;
+  NmsLayout(FsfArena& arena, int64_t n)
+      : words((n + 63) / 64), sum_words((words + 63) / 64), mask(arena.take<uint64_t>((n > 0 ? n : 1) * (words > 0 ? words : 1))),
+        rowsum(arena.take<uint64_t>((n > 0 ? n : 1) * (sum_words > 0 ? sum_words : 1))), tmp(arena.take<int64_t>(1)),
+        bins(nms_bins_layout(arena, n)) {}
+};
+
+extern "C" int64_t fsf_nms_bev_workspace_bytes(int64_t n) { return fsf_layout_bytes<NmsLayout>(n); }
 
 extern "C" int fsf_nms_bev(const float* boxes, int64_t n, float thresh, int32_t rotated, int64_t* keep,
                            int64_t* num_keep_dev, int64_t* num_keep_host, void* workspace, int64_t workspace_bytes,
@@ -434,20 +440,15 @@ extern "C" int fsf_nms_bev(const float* boxes, int64_t n, float thresh, int32_t 
   if (n < 0 || (n > 0 && (!boxes || !keep)) || (!num_keep_dev && !num_keep_host)) return FSF_ERR_INVALID_ARG;
   const int64_t words = (n + 63) / 64;
   if (words * 8 > 60 * 1024) return FSF_ERR_UNSUPPORTED;  // `removed` bitset lives in LDS (n <= 491520)
-  if (workspace_bytes < fsf_nms_bev_workspace_bytes(n) || !workspace) return FSF_ERR_WORKSPACE;
-  FsfArena arena(workspace, workspace_bytes);
-  const int64_t sum_words = (words + 63) / 64;
-  uint64_t* mask = arena.take<uint64_t>((n > 0 ? n : 1) * (words > 0 ? words : 1));
-  uint64_t* rowsum = arena.take<uint64_t>((n > 0 ? n : 1) * (sum_words > 0 ? sum_words : 1));
-  int64_t* tmp = arena.take<int64_t>(1);
-  if (!arena.ok()) return FSF_ERR_WORKSPACE;
-  int64_t* ndev = num_keep_dev ? num_keep_dev : tmp;
+  FSF_CARVE(NmsLayout, l, workspace, workspace_bytes, n);
+  const int64_t sum_words = l.sum_words;
+  int64_t* ndev = num_keep_dev ? num_keep_dev : l.tmp;
   if (n == 0) {
     FSF_HIP_TRY(hipMemsetAsync(ndev, 0, sizeof(int64_t), stream));
   } else {
-    NmsArgs a{boxes, n, thresh, (int)rotated, mask, rowsum, (int)words, (int)sum_words, keep, ndev, nullptr, 0, 0, 0, 0, 0, nullptr};
-    FSF_HIP_TRY(hipMemsetAsync(rowsum, 0, (size_t)n * sum_words * 8, stream));
-    const int rc = nms_launch_mask(a, arena, stream);
+    NmsArgs a{boxes, n, thresh, (int)rotated, l.mask, l.rowsum, (int)words, (int)sum_words, keep, ndev, nullptr, 0, 0, 0, 0, 0, nullptr};
+    FSF_HIP_TRY(hipMemsetAsync(l.rowsum, 0, (size_t)n * sum_words * 8, stream));
+    const int rc = nms_launch_mask(a, l.bins, stream);
     if (rc != FSF_OK) return rc;
     hipLaunchKernelGGL(nms_scan_kernel, dim3(1), dim3(256), (size_t)words * 8, stream, a);
     FSF_LAUNCH_CHECK();
@@ -465,24 +466,30 @@ static int64_t nms_window(int64_t n, int64_t max_keep, bool windowed) {
   return k < n ? k : n;
 }
 
-static int64_t nms_multiclass_bytes(int64_t n, int32_t num_classes, int64_t rows) {
-  const int64_t words = (n + 63) / 64, sum_words = (words + 63) / 64;
-  const int64_t cw = (rows + 63) / 64, cs = (cw + 63) / 64;
-  const int64_t n1 = n > 0 ? n : 1, w1 = words > 0 ? words : 1, s1 = sum_words > 0 ? sum_words : 1;
-  const int64_t r1 = rows > 0 ? rows : 1, cw1 = cw > 0 ? cw : 1, cs1 = cs > 0 ? cs : 1;
-  const int64_t c1 = num_classes > 0 ? num_classes : 1;
-  return fsf_align_up(n1 * w1 * 8, 256) + fsf_align_up(n1 * s1 * 8, 256) + fsf_align_up(c1 * r1 * cw1 * 8, 256) +
-         fsf_align_up(c1 * r1 * cs1 * 8, 256) + 512 + nms_bins_bytes(n);
-}
+// [mask0 | rowsum0 | mask | rowsum | bins] is everything that must start at zero, in one piece from the arena's start: ONE clear
+// (the build kernel walks mask0 through rowsum0, so the lower-triangle words the mask kernel skips are never read)
+struct NmsMulticlassLayout {
+  int64_t words, sum_words, cwords, csum;
+  uint64_t *mask0, *rowsum0, *mask, *rowsum;
+  NmsBins bins;
+  int64_t clear_bytes;
+  NmsMulticlassLayout(FsfArena& arena, int64_t n, int64_t classes, int64_t rows)
+      : words((n + 63) / 64), sum_words((words + 63) / 64), cwords((rows + 63) / 64), csum((cwords + 63) / 64),
+        mask0(arena.take<uint64_t>((n > 0 ? n : 1) * (words > 0 ? words : 1))),
+        rowsum0(arena.take<uint64_t>((n > 0 ? n : 1) * (sum_words > 0 ? sum_words : 1))),
+        mask(arena.take<uint64_t>((classes > 0 ? classes : 1) * (rows > 0 ? rows : 1) * (cwords > 0 ? cwords : 1))),
+        rowsum(arena.take<uint64_t>((classes > 0 ? classes : 1) * (rows > 0 ? rows : 1) * (csum > 0 ? csum : 1))),
+        bins(nms_bins_layout(arena, n)), clear_bytes(arena.offset()) {}
+};
 
 extern "C" int64_t fsf_nms_bev_multiclass_workspace_bytes(int64_t n, int32_t num_classes) {
-  return nms_multiclass_bytes(n, num_classes, n);
+  return fsf_layout_bytes<NmsMulticlassLayout>(n, (int64_t)num_classes, n);
 }
 
 // with a cap AND an `incomplete` flag the per-class masks only hold each class's best window = max(4 max_keep, 2048) boxes:
 // (1 + C (window / n)^2) n^2 / 8 bytes instead of (1 + C) n^2 / 8
 extern "C" int64_t fsf_nms_bev_multiclass_capped_workspace_bytes(int64_t n, int32_t num_classes, int64_t max_keep) {
-  return nms_multiclass_bytes(n, num_classes, nms_window(n, max_keep, true));
+  return fsf_layout_bytes<NmsMulticlassLayout>(n, (int64_t)num_classes, nms_window(n, max_keep, true));
 }
 
 extern "C" int fsf_nms_bev_multiclass_capped(const float* boxes, int64_t n, int32_t num_classes, const int32_t* rank,
@@ -507,37 +514,22 @@ extern "C" int fsf_nms_bev_multiclass_capped(const float* boxes, int64_t n, int3
   if (words * 8 > 60 * 1024) return FSF_ERR_UNSUPPORTED;
   const bool windowed = incomplete != nullptr && max_keep > 0;
   const int64_t rows = nms_window(n, max_keep, windowed);
-  const int64_t cwords = (rows + 63) / 64, csum = (cwords + 63) / 64;
-  if (workspace_bytes < nms_multiclass_bytes(n, num_classes, rows) || !workspace) return FSF_ERR_WORKSPACE;
+  FSF_CARVE(NmsMulticlassLayout, l, workspace, workspace_bytes, n, num_classes, rows);
   if (incomplete) FSF_HIP_TRY(hipMemsetAsync(incomplete, 0, sizeof(int32_t), stream));
   if (n == 0) {
     FSF_HIP_TRY(hipMemsetAsync(num_keep, 0, sizeof(int64_t) * num_classes, stream));
     return FSF_OK;
   }
-  FsfArena arena(workspace, workspace_bytes);
-  uint64_t* mask0 = arena.take<uint64_t>(n * words);
-  uint64_t* rowsum0 = arena.take<uint64_t>(n * sum_words);
-  uint64_t* mask = arena.take<uint64_t>((int64_t)num_classes * rows * cwords);
-  uint64_t* rowsum = arena.take<uint64_t>((int64_t)num_classes * rows * csum);
-  if (!arena.ok()) return FSF_ERR_WORKSPACE;
-  // ONE clear for everything that must start at zero: the four arrays above (the build kernel walks mask0 through rowsum0, so the
-  // lower-triangle words the mask kernel skips are never read) and, right behind them in the arena, the cell counters / lists
-  // nms_launch_mask takes (six memsets before)
-  const int64_t clear_bytes = std::min<int64_t>(arena.used + nms_bins_bytes(n), workspace_bytes);
-  FSF_HIP_TRY(hipMemsetAsync(mask0, 0, (size_t)clear_bytes, stream));
-  NmsArgs a0{boxes, n, thresh, (int)rotated, mask0, rowsum0, (int)words, (int)sum_words, nullptr, nullptr, nullptr, 0, 0, 0, 0, 0, nullptr};
-  const int64_t used_before = arena.used;
-  const int rc = nms_launch_mask(a0, arena, stream, true);
+  FSF_HIP_TRY(hipMemsetAsync(l.mask0, 0, (size_t)l.clear_bytes, stream));  // (six memsets before)
+  NmsArgs a0{boxes, n, thresh, (int)rotated, l.mask0, l.rowsum0, (int)words, (int)sum_words, nullptr, nullptr, nullptr, 0, 0, 0, 0, 0, nullptr};
+  const int rc = nms_launch_mask(a0, l.bins, stream, true);
   if (rc != FSF_OK) return rc;
-  // the single clear above covers what nms_launch_mask took only if it took it right behind the four arrays and no more
-  // than nms_bins_bytes(n): a layout change there must fail here, not read uncleared counters
-  if (arena.used - used_before > nms_bins_bytes(n) || arena.used > clear_bytes) return FSF_ERR_WORKSPACE;
-  NmsBuildArgs b{mask0, rowsum0, rank, mask, rowsum, n, (int)words, (int)sum_words, rows, (int)cwords, (int)csum};
+  NmsBuildArgs b{l.mask0, l.rowsum0, rank, l.mask, l.rowsum, n, (int)words, (int)sum_words, rows, (int)l.cwords, (int)l.csum};
   hipLaunchKernelGGL(nms_build_kernel, dim3((unsigned)fsf_stream_grid(n * sum_words, 256), (unsigned)num_classes), dim3(256), 0,
                      stream, b);
-  NmsArgs a{boxes, n, thresh, (int)rotated, mask, rowsum, (int)cwords, (int)csum, keep, num_keep, count,
-            rows * cwords, rows * csum, n, max_keep, windowed ? rows : 0, incomplete};
-  hipLaunchKernelGGL(nms_scan_kernel, dim3((unsigned)num_classes), dim3(256), (size_t)cwords * 8, stream, a);
+  NmsArgs a{boxes, n, thresh, (int)rotated, l.mask, l.rowsum, (int)l.cwords, (int)l.csum, keep, num_keep, count,
+            rows * l.cwords, rows * l.csum, n, max_keep, windowed ? rows : 0, incomplete};
+  hipLaunchKernelGGL(nms_scan_kernel, dim3((unsigned)num_classes), dim3(256), (size_t)l.cwords * 8, stream, a);
   FSF_LAUNCH_CHECK();
   return FSF_OK;
 }

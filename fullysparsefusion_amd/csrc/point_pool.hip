@@ -476,12 +476,35 @@ __global__ void pool_count_kernel(const uint32_t* total, int64_t max_all, int64_
 
 using namespace fsf;
 
+struct PoolLayout {
+  int pt_tiles;
+  int64_t r1;
+  uint32_t *cnt, *roi_total, *roi_off, *tile_sums, *total;
+  int64_t* count_tmp;
+  uint32_t* chunk_total;
+  // the binned path only (`binned`): the sort, the cell tables and the sorted points
+  uint32_t* hits_full = nullptr;
+  RadixScratch sort;
+  // [sort.hist | cell_start | cell_end | the scan's tile words] are consecutive: ONE memset instead of four
+  uint32_t *cell_start = nullptr, *cell_end = nullptr, *tile_sums_b = nullptr;
+  size_t zero_bytes = 0;
+  float4* sorted = nullptr;
+  PoolLayout(FsfArena& arena, int64_t n_pts, int64_t n_rois, bool binned)
+      : pt_tiles(n_pts > 0 ? fsf_cdiv(n_pts, PP_TILE) : 1), r1(n_rois > 0 ? n_rois : 1), cnt(arena.take<uint32_t>((int64_t)pt_tiles * r1)),
+        roi_total(arena.take<uint32_t>(r1)), roi_off(arena.take<uint32_t>(r1)), tile_sums(arena.take<uint32_t>(scan_num_tiles(r1))),
+        total(arena.take<uint32_t>(1)), count_tmp(arena.take<int64_t>(1)), chunk_total(arena.take<uint32_t>(32)),
+        hits_full(binned ? arena.take<uint32_t>(r1) : nullptr), sort(binned ? RadixScratch(arena, n_pts) : RadixScratch()) {
+    if (!binned) return;
+    cell_start = arena.take<uint32_t>(PB_NCELL);
+    cell_end = arena.take<uint32_t>(PB_NCELL);
+    tile_sums_b = arena.take<uint32_t>(scan_num_tiles(r1));
+    zero_bytes = (size_t)(arena.offset() - sort.hist_at);
+    sorted = arena.take<float4>(n_pts);
+  }
+};
+
 extern "C" int64_t fsf_dynamic_point_pool_workspace_bytes(int64_t n_pts, int64_t n_rois) {
-  const int64_t pt_tiles = n_pts > 0 ? (n_pts + PP_TILE - 1) / PP_TILE : 1;
-  const int64_t r = n_rois > 0 ? n_rois : 1;
-  return fsf_align_up(pt_tiles * r * 4, 256) + 3 * fsf_align_up(r * 4, 256) + 2 * fsf_align_up(scan_num_tiles(r) * 4, 256) + 768 +
-         radix_sort_scratch_bytes(n_pts) + 2 * fsf_align_up((int64_t)PB_NCELL * 4, 256) +
-         fsf_align_up((n_pts > 0 ? n_pts : 1) * 16, 256);  // (+ the binned path's sort, cell tables and sorted points)
+  return fsf_layout_bytes<PoolLayout>(n_pts, n_rois, true);
 }
 
 extern "C" int fsf_dynamic_point_pool(const float* rois, int64_t n_rois, int32_t roi_stride, int32_t box_col,
@@ -496,79 +519,56 @@ extern "C" int fsf_dynamic_point_pool(const float* rois, int64_t n_rois, int32_t
       !out_pts_feats || (!count_dev && !count_host) || (n_rois > 0 && !rois) || (n_pts > 0 && !pts))
     return FSF_ERR_INVALID_ARG;
   if (n_pts >= ((int64_t)1 << 31) || n_rois >= ((int64_t)1 << 31)) return FSF_ERR_UNSUPPORTED;
-  if (workspace_bytes < fsf_dynamic_point_pool_workspace_bytes(n_pts, n_rois) || !workspace) return FSF_ERR_WORKSPACE;
-  FsfArena arena(workspace, workspace_bytes);
-  const int pt_tiles = n_pts > 0 ? fsf_cdiv(n_pts, PP_TILE) : 1;
-  const int64_t r1 = n_rois > 0 ? n_rois : 1;
-  uint32_t* cnt = arena.take<uint32_t>((int64_t)pt_tiles * r1);
-  uint32_t* roi_total = arena.take<uint32_t>(r1);
-  uint32_t* roi_off = arena.take<uint32_t>(r1);
-  uint32_t* tile_sums = arena.take<uint32_t>(scan_num_tiles(r1));
-  uint32_t* total = arena.take<uint32_t>(1);
-  int64_t* count_tmp = arena.take<int64_t>(1);
-  uint32_t* chunk_total = arena.take<uint32_t>(32);
-  if (!arena.ok()) return FSF_ERR_WORKSPACE;
-  int64_t* cdev = count_dev ? count_dev : count_tmp;
+  const bool brute = g_opt_pool_brute.load(std::memory_order_relaxed) != 0;  // (fsf_set_option: tests compare the two paths in one process)
+  FSF_CARVE(PoolLayout, l, workspace, workspace_bytes, n_pts, n_rois, !brute && max_inbox_point <= PB_CAP);
+  int64_t* cdev = count_dev ? count_dev : l.count_tmp;
   if (n_rois == 0 || n_pts == 0) {
     FSF_HIP_TRY(hipMemsetAsync(cdev, 0, sizeof(int64_t), stream));
   } else {
     PoolArgs a{rois, pts, pts_batch, n_rois, n_pts, (int)roi_stride, (int)box_col, (int)batch_col, (int)pts_stride,
-               extra_wlh[0], extra_wlh[1], extra_wlh[2], (int)max_inbox_point, max_all_pts, cnt, roi_total, roi_off,
-               out_pts_idx, out_roi_idx, out_pts_feats, 0, 0, chunk_total};
-    if (!arena.ok()) return FSF_ERR_WORKSPACE;
-    const bool brute = g_opt_pool_brute.load(std::memory_order_relaxed) != 0;  // (fsf_set_option: tests compare the two paths in one process)
+               extra_wlh[0], extra_wlh[1], extra_wlh[2], (int)max_inbox_point, max_all_pts, l.cnt, l.roi_total, l.roi_off,
+               out_pts_idx, out_roi_idx, out_pts_feats, 0, 0, l.chunk_total};
     if (!brute && max_inbox_point <= PB_CAP) {
-      uint32_t* hits_full = arena.take<uint32_t>(r1);
-      uint64_t* keys_a = arena.take<uint64_t>(n_pts);
-      uint64_t* keys_b = arena.take<uint64_t>(n_pts);
-      uint32_t* vals_a = arena.take<uint32_t>(n_pts);
-      uint32_t* vals_b = arena.take<uint32_t>(n_pts);
-      // [sort histograms | cell_start | cell_end | the scan's tile words] are consecutive: ONE memset instead of four
-      uint32_t* hist = arena.take<uint32_t>((radix_num_tiles(n_pts) + 1) * RS_BINS);
-      uint32_t* cell_start = arena.take<uint32_t>(PB_NCELL);
-      uint32_t* cell_end = arena.take<uint32_t>(PB_NCELL);
-      uint32_t* tile_sums_b = arena.take<uint32_t>(scan_num_tiles(r1));
-      float4* sorted = arena.take<float4>(n_pts);
-      if (!arena.ok()) return FSF_ERR_WORKSPACE;
-      FSF_HIP_TRY(hipMemsetAsync(hist, 0, (size_t)((char*)sorted - (char*)hist), stream));
+      const RadixScratch& s = l.sort;
+      FSF_HIP_TRY(hipMemsetAsync(s.hist, 0, l.zero_bytes, stream));
       hipLaunchKernelGGL(pb_keys_kernel, dim3((unsigned)fsf_stream_grid(n_pts, 256)), dim3(256), 0, stream, pts, n_pts, (int)pts_stride,
-                         keys_a, vals_a);
+                         s.keys_a, s.vals_a);
       uint64_t* keys = nullptr;
       uint32_t* order = nullptr;
-      int rc = radix_sort_pairs(keys_a, vals_a, keys_b, vals_b, hist, n_pts, 2 * PB_BITS, &keys, &order, stream, true);
+      int rc = radix_sort_pairs(s.keys_a, s.vals_a, s.keys_b, s.vals_b, s.hist, n_pts, 2 * PB_BITS, &keys, &order, stream, true);
       if (rc != FSF_OK) return rc;
       hipLaunchKernelGGL(pb_cells_kernel, dim3((unsigned)fsf_stream_grid(n_pts, 256)), dim3(256), 0, stream, keys, order, n_pts, pts,
-                         (int)pts_stride, pts_batch, cell_start, cell_end, sorted);
-      PoolBinArgs b{a, order, sorted, cell_start, cell_end, hits_full};
+                         (int)pts_stride, pts_batch, l.cell_start, l.cell_end, l.sorted);
+      PoolBinArgs b{a, order, l.sorted, l.cell_start, l.cell_end, l.hits_full};
       const unsigned wg = (unsigned)((n_rois + 3) / 4);
       hipLaunchKernelGGL(pb_count_kernel, dim3(wg), dim3(256), 0, stream, b);
-      rc = exclusive_scan_u32(PoolScanIn{roi_total}, PoolScanOut{roi_off}, n_rois, tile_sums_b, total, nullptr, stream, (int64_t)max_inbox_point, true);
+      rc = exclusive_scan_u32(PoolScanIn{l.roi_total}, PoolScanOut{l.roi_off}, n_rois, l.tile_sums_b, l.total, nullptr, stream, (int64_t)max_inbox_point, true);
       if (rc != FSF_OK) return rc;
       hipLaunchKernelGGL(pb_fill_kernel, dim3(wg), dim3(256), 0, stream, b);
-      hipLaunchKernelGGL(pool_count_kernel, dim3(1), dim3(1), 0, stream, total, max_all_pts, cdev);
+      hipLaunchKernelGGL(pool_count_kernel, dim3(1), dim3(1), 0, stream, l.total, max_all_pts, cdev);
       FSF_LAUNCH_CHECK();
       if (count_host) {
         FSF_READ_BACK(count_host, cdev, sizeof(int64_t), stream);
       }
       return FSF_OK;
     }
-    FSF_HIP_TRY(hipMemsetAsync(roi_total, 0, sizeof(uint32_t) * n_rois, stream));
-    FSF_HIP_TRY(hipMemsetAsync(chunk_total, 0, sizeof(uint32_t) * 32, stream));
+    FSF_HIP_TRY(hipMemsetAsync(l.roi_total, 0, sizeof(uint32_t) * n_rois, stream));
+    FSF_HIP_TRY(hipMemsetAsync(l.chunk_total, 0, sizeof(uint32_t) * 32, stream));
     const int groups = fsf_cdiv(n_rois, 256);
     for (int g0 = 0, len = 1, chunk = 0; g0 < groups; g0 += len, len = chunk < 30 ? len * 2 : groups, ++chunk) {
       const int ng = g0 + len <= groups ? len : groups - g0;
       a.group0 = g0;
       a.chunk = chunk;
-      hipLaunchKernelGGL((pool_pass_kernel<false>), dim3((unsigned)ng, (unsigned)pt_tiles), dim3(256), 0, stream, a);
-      hipLaunchKernelGGL(pool_prefix_kernel, dim3((unsigned)ng), dim3(256), 0, stream, a, pt_tiles);
+      hipLaunchKernelGGL((pool_pass_kernel<false>), dim3((unsigned)ng, (unsigned)l.pt_tiles), dim3(256), 0, stream, a);
+      hipLaunchKernelGGL(pool_prefix_kernel, dim3((unsigned)ng), dim3(256), 0, stream, a, l.pt_tiles);
     }
     a.group0 = 0;
     a.chunk = 0;
-    const dim3 grid((unsigned)groups, (unsigned)pt_tiles);
-    int rc = exclusive_scan_u32(PoolScanIn{roi_total}, PoolScanOut{roi_off}, n_rois, tile_sums, total, nullptr, stream, (int64_t)max_inbox_point);
+    const dim3 grid((unsigned)groups, (unsigned)l.pt_tiles);
+    int rc = exclusive_scan_u32(PoolScanIn{l.roi_total}, PoolScanOut{l.roi_off}, n_rois, l.tile_sums, l.total, nullptr, stream, (int64_t)max_inbox_point);
     if (rc != FSF_OK) return rc;
     hipLaunchKernelGGL((pool_pass_kernel<true>), grid, dim3(256), 0, stream, a);
-    hipLaunchKernelGGL(pool_count_kernel, dim3(1), dim3(1), 0, stream, total, max_all_pts, cdev);
+    hipLaunchKernelGGL(pool_count_kernel, dim3(1), dim3(1), 0, stream, l.total, max_all_pts, cdev);
     FSF_LAUNCH_CHECK();
   }
   if (count_host) {

@@ -561,38 +561,18 @@ __global__ void __launch_bounds__(256) ov_extra_rows_kernel(OvRowsArgs a) {
 
 struct OvLayout {
   uint32_t* fg_idx;
-  uint64_t *keys_a, *keys_b;
-  uint32_t *vals_a, *vals_b;
-  uint32_t* hist;
+  RadixScratch sort;  // [sort.hist | tile_sums | ret] are consecutive: one memset
   uint32_t* tile_sums;
   int64_t* ret;
-  int32_t* table;
   size_t zero_bytes;
-  bool ok;
+  int32_t* table;
+  OvLayout(FsfArena& ar, int64_t n)
+      : fg_idx(ar.take<uint32_t>(n)), sort(ar, n), tile_sums(ar.take<uint32_t>(scan_num_tiles(n))), ret(ar.take<int64_t>(4)),
+        zero_bytes((size_t)(ar.offset() - sort.hist_at)), table(ar.take<int32_t>(3 * 256)) {}
 };
-static OvLayout ov_layout(void* ws, int64_t ws_bytes, int64_t n) {
-  FsfArena ar(ws, ws_bytes);
-  OvLayout l;
-  l.fg_idx = ar.take<uint32_t>(n);
-  l.keys_a = ar.take<uint64_t>(n);
-  l.keys_b = ar.take<uint64_t>(n);
-  l.vals_a = ar.take<uint32_t>(n);
-  l.vals_b = ar.take<uint32_t>(n);
-  l.hist = ar.take<uint32_t>((radix_num_tiles(n) + 1) * RS_BINS);  // [hist | tile_sums | ret] are consecutive: one memset
-  l.tile_sums = ar.take<uint32_t>(scan_num_tiles(n));
-  l.ret = ar.take<int64_t>(4);
-  l.table = ar.take<int32_t>(3 * 256);
-  l.zero_bytes = (size_t)((char*)l.table - (char*)l.hist);
-  l.ok = ar.ok();
-  return l;
-}
 }  // namespace fsf
 
-extern "C" int64_t fsf_overlap_plan_workspace_bytes(int64_t n) {
-  const int64_t m = n > 0 ? n : 1;
-  return fsf_align_up(m * 4, 256) * 3 + fsf_align_up(m * 8, 256) * 2 + fsf_align_up((radix_num_tiles(n) + 1) * RS_BINS * 4, 256) +
-         fsf_align_up(scan_num_tiles(n) * 4, 256) + 256 + fsf_align_up(3 * 256 * 4, 256);
-}
+extern "C" int64_t fsf_overlap_plan_workspace_bytes(int64_t n) { return fsf_layout_bytes<OvLayout>(n); }
 
 extern "C" int fsf_overlap_plan(const uint8_t* fg, const uint8_t* count, int64_t n, int32_t max_cells, int64_t* counts_host, void* workspace,
                                 int64_t workspace_bytes, void* stream_) {
@@ -601,17 +581,16 @@ extern "C" int fsf_overlap_plan(const uint8_t* fg, const uint8_t* count, int64_t
   if (max_cells < 1 || max_cells > 254 || n >= ((int64_t)1 << 31)) return FSF_ERR_UNSUPPORTED;  // (a u8 count must not saturate)
   counts_host[0] = counts_host[1] = counts_host[2] = 0;
   if (n == 0) return FSF_OK;
-  if (!workspace || workspace_bytes < fsf_overlap_plan_workspace_bytes(n)) return FSF_ERR_WORKSPACE;
-  const OvLayout l = ov_layout(workspace, workspace_bytes, n);
-  if (!l.ok) return FSF_ERR_WORKSPACE;
-  FSF_HIP_TRY(hipMemsetAsync(l.hist, 0, l.zero_bytes, stream));
-  int rc = exclusive_scan_u32(OvIn{fg, count, l.keys_a, l.vals_a}, OvOut{l.fg_idx}, n, l.tile_sums, nullptr, l.ret, stream, 1, true);
+  FSF_CARVE(OvLayout, l, workspace, workspace_bytes, n);
+  const RadixScratch& s = l.sort;
+  FSF_HIP_TRY(hipMemsetAsync(s.hist, 0, l.zero_bytes, stream));
+  int rc = exclusive_scan_u32(OvIn{fg, count, s.keys_a, s.vals_a}, OvOut{l.fg_idx}, n, l.tile_sums, nullptr, l.ret, stream, 1, true);
   if (rc != FSF_OK) return rc;
   uint64_t* keys_s;
   uint32_t* vals_s;
-  rc = radix_sort_pairs(l.keys_a, l.vals_a, l.keys_b, l.vals_b, l.hist, n, 8, &keys_s, &vals_s, stream, true);
+  rc = radix_sort_pairs(s.keys_a, s.vals_a, s.keys_b, s.vals_b, s.hist, n, 8, &keys_s, &vals_s, stream, true);
   if (rc != FSF_OK) return rc;
-  if (keys_s != l.keys_b || vals_s != l.vals_b) return FSF_ERR_UNSUPPORTED;  // (one pass: fsf_overlap_rows reads the alternate buffers)
+  if (keys_s != s.keys_b || vals_s != s.vals_b) return FSF_ERR_UNSUPPORTED;  // (one pass: fsf_overlap_rows reads the alternate buffers)
   hipLaunchKernelGGL(ov_plan_kernel, dim3(1), dim3(256), 0, stream, keys_s, n, l.table, l.ret);
   FSF_LAUNCH_CHECK();
   int64_t ret_h[4] = {0, 0, 0, 0};
@@ -633,11 +612,9 @@ extern "C" int fsf_overlap_rows(const float* xyz, int64_t n, int32_t xyz_stride,
       (num_fg > 0 && (!xyz || !max_id || !src_pt || !sir_coors)))
     return FSF_ERR_INVALID_ARG;
   if (num_fg == 0) return FSF_OK;
-  if (!workspace || workspace_bytes < fsf_overlap_plan_workspace_bytes(n)) return FSF_ERR_WORKSPACE;
-  const OvLayout l = ov_layout(const_cast<void*>(workspace), workspace_bytes, n);
-  if (!l.ok) return FSF_ERR_WORKSPACE;
+  FSF_CARVE(OvLayout, l, const_cast<void*>(workspace), workspace_bytes, n);
   (void)num_extra;
-  OvRowsArgs a{xyz, lidar2img, mask, max_id, batch_idx, l.fg_idx, l.keys_b, l.vals_b, l.table, src_pt, sir_coors, n, num_fg, num_multi,
+  OvRowsArgs a{xyz, lidar2img, mask, max_id, batch_idx, l.fg_idx, l.sort.keys_b, l.sort.vals_b, l.table, src_pt, sir_coors, n, num_fg, num_multi,
                (int)xyz_stride, (int)ncam, (int)ncls, (int)img_h, (int)img_w};
   hipLaunchKernelGGL(ov_own_rows_kernel, dim3(fsf_stream_grid(num_fg, 256)), dim3(256), 0, stream, a);
   if (num_multi > 0) {

@@ -178,26 +178,12 @@ __global__ void __launch_bounds__(256) bilinear_bwd_sum_kernel(BilinBwdSumArgs a
 }
 
 struct BilinBwdLayout {
-  uint64_t *keys_a, *keys_b;
-  uint32_t *vals_a, *vals_b;
-  uint32_t* hist;
+  RadixScratch sort;
   float2* frac;
   uint32_t* start;
-  bool ok;
+  BilinBwdLayout(FsfArena& ar, int64_t total, int64_t num_cells)
+      : sort(ar, total), frac(ar.take<float2>(total)), start(ar.take<uint32_t>(num_cells + 1)) {}
 };
-static BilinBwdLayout bilinear_bwd_layout(void* ws, int64_t ws_bytes, int64_t total, int64_t num_cells) {
-  FsfArena ar(ws, ws_bytes);
-  BilinBwdLayout l;
-  l.keys_a = ar.take<uint64_t>(total);
-  l.keys_b = ar.take<uint64_t>(total);
-  l.vals_a = ar.take<uint32_t>(total);
-  l.vals_b = ar.take<uint32_t>(total);
-  l.hist = ar.take<uint32_t>((radix_num_tiles(total) + 1) * RS_BINS);
-  l.frac = ar.take<float2>(total);
-  l.start = ar.take<uint32_t>(num_cells + 1);
-  l.ok = ar.ok();
-  return l;
-}
 
 // 0: fine; otherwise the status the arguments earn (shared by the size function, which answers 0 bytes to them)
 static int bilinear_bwd_shape_status(int64_t n, int32_t ncam, int32_t feat_h, int32_t feat_w, int32_t channels) {
@@ -214,8 +200,7 @@ using namespace fsf;
 extern "C" int64_t fsf_project_gather_bilinear_backward_workspace_bytes(int64_t n, int32_t ncam, int32_t feat_h, int32_t feat_w,
                                                                         int32_t channels) {
   if (bilinear_bwd_shape_status(n, ncam, feat_h, feat_w, channels) != FSF_OK) return 0;
-  const int64_t total = n * ncam, num_cells = (int64_t)ncam * (feat_h + 1) * (feat_w + 1);
-  return radix_sort_scratch_bytes(total) + fsf_align_up((total > 0 ? total : 1) * 8, 256) + fsf_align_up((num_cells + 1) * 4, 256);
+  return fsf_layout_bytes<BilinBwdLayout>(n * ncam, (int64_t)ncam * (feat_h + 1) * (feat_w + 1));
 }
 
 extern "C" int fsf_project_gather_bilinear_backward(const float* xyz, int64_t n, int32_t xyz_stride, const float* lidar2img, int32_t ncam,
@@ -228,24 +213,22 @@ extern "C" int fsf_project_gather_bilinear_backward(const float* xyz, int64_t n,
     return FSF_ERR_INVALID_ARG;
   const int rc_shape = bilinear_bwd_shape_status(n, ncam, feat_h, feat_w, channels);
   if (rc_shape != FSF_OK) return rc_shape;
-  if (!workspace || workspace_bytes < fsf_project_gather_bilinear_backward_workspace_bytes(n, ncam, feat_h, feat_w, channels))
-    return FSF_ERR_WORKSPACE;
   const int64_t total = n * ncam, num_cells = (int64_t)ncam * (feat_h + 1) * (feat_w + 1);
+  FSF_CARVE(BilinBwdLayout, l, workspace, workspace_bytes, total, num_cells);
+  const RadixScratch& s = l.sort;
   const int64_t texels = (int64_t)ncam * feat_h * feat_w;
   if (n == 0) {  // no taps: the all-zero map
     FSF_HIP_TRY(hipMemsetAsync(grad_feat, 0, (size_t)texels * channels * sizeof(float), stream));
     return FSF_OK;
   }
-  const BilinBwdLayout l = bilinear_bwd_layout(workspace, workspace_bytes, total, num_cells);
-  if (!l.ok) return FSF_ERR_WORKSPACE;
-  BilinBwdKeyArgs ka{xyz, lidar2img, l.keys_a, l.vals_a, l.frac, total, (int)xyz_stride, (int)ncam, (int)feat_h, (int)feat_w, (int)img_h, (int)img_w};
+  BilinBwdKeyArgs ka{xyz, lidar2img, s.keys_a, s.vals_a, l.frac, total, (int)xyz_stride, (int)ncam, (int)feat_h, (int)feat_w, (int)img_h, (int)img_w};
   hipLaunchKernelGGL(bilinear_bwd_keys_kernel, dim3(fsf_stream_grid(total, 256)), dim3(256), (size_t)ncam * 12 * sizeof(float), stream, ka);
   FSF_LAUNCH_CHECK();
   int key_bits = 1;
   while (((int64_t)1 << key_bits) <= num_cells) ++key_bits;  // the sentinel NC itself is a key
   uint64_t* keys_s = nullptr;
   uint32_t* vals_s = nullptr;
-  const int rc = radix_sort_pairs(l.keys_a, l.vals_a, l.keys_b, l.vals_b, l.hist, total, key_bits, &keys_s, &vals_s, stream);
+  const int rc = radix_sort_pairs(s.keys_a, s.vals_a, s.keys_b, s.vals_b, s.hist, total, key_bits, &keys_s, &vals_s, stream);
   if (rc != FSF_OK) return rc;
   hipLaunchKernelGGL(bilinear_bwd_starts_kernel, dim3(fsf_stream_grid(num_cells + 1, 256)), dim3(256), 0, stream, keys_s, total, num_cells,
                      l.start);

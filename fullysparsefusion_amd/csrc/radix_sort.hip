@@ -239,12 +239,6 @@ __global__ void __launch_bounds__(RS_THREADS)
   }
 }
 
-int64_t radix_sort_scratch_bytes(int64_t n) {
-  int64_t nn = n > 0 ? n : 1;
-  return fsf_align_up(nn * 8, 256) * 2 + fsf_align_up(nn * 4, 256) * 2 +
-         fsf_align_up((radix_num_tiles(n) + 1) * RS_BINS * 4, 256);  // (radix_num_tiles counts the one-sweep status words in)
-}
-
 int radix_sort_pairs(uint64_t* keys_a, uint32_t* vals_a, uint64_t* keys_b, uint32_t* vals_b, uint32_t* hist,
                      int64_t n, int key_bits, uint64_t** keys_out, uint32_t** vals_out, hipStream_t stream, bool hist_zeroed) {
   uint64_t* kin = keys_a;

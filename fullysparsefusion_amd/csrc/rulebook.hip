@@ -332,13 +332,28 @@ static int bit_width64(uint64_t v) {
 
 using namespace fsf;
 
+// the strided rulebook: input table + candidate set / out table + candidate list and its sort scratch
+struct RbStridedLayout {
+  // (the two key tables back to back — capacities are powers of two >= 2, so both stay 256-byte aligned: ONE fill launch)
+  uint64_t* in_keys;
+  int32_t *in_vals, *set_vals;
+  RadixScratch list;  // keys_a / vals_a: the candidate list
+  uint32_t* count_dev;
+  RbStridedLayout(FsfArena& ar, int64_t in_cap, int64_t set_cap, int64_t cand)
+      : in_keys(ar.take<uint64_t>(in_cap + set_cap)), in_vals(ar.take<int32_t>(in_cap)), set_vals(ar.take<int32_t>(set_cap)),
+        list(ar, cand), count_dev(ar.take<uint32_t>(1)) {}
+};
+// the submanifold rulebook: the input table alone
+struct RbSubmLayout {
+  uint64_t* keys;
+  int32_t* vals;
+  RbSubmLayout(FsfArena& ar, int64_t cap) : keys(ar.take<uint64_t>(cap)), vals(ar.take<int32_t>(cap)) {}
+};
+
+// ONE query for both rulebooks: the strided layout with every offset proposing its own site, which the submanifold one fits inside
 extern "C" int64_t fsf_rulebook_workspace_bytes(int64_t m_in, int32_t kvol) {
-  const int64_t m = m_in > 0 ? m_in : 1;
-  const int64_t in_cap = (int64_t)pow2_at_least((uint64_t)m * 2);
-  const int64_t cand = m * kvol;
-  const int64_t set_cap = (int64_t)pow2_at_least((uint64_t)cand * 2);
-  // input table + candidate set/out table + candidate list (x2 for sort) + sort scratch
-  return fsf_align_up(in_cap * 12, 256) + fsf_align_up(set_cap * 12, 256) + radix_sort_scratch_bytes(cand) + 8 * 256;
+  const int64_t m = m_in > 0 ? m_in : 1, cand = m * kvol;
+  return fsf_layout_bytes<RbStridedLayout>((int64_t)pow2_at_least((uint64_t)m * 2), (int64_t)pow2_at_least((uint64_t)cand * 2), cand);
 }
 
 static int make_geom(ConvGeom* g, int32_t batch_size, const int32_t shape[3], const int32_t ksize[3],
@@ -381,17 +396,16 @@ extern "C" int fsf_rulebook_subm(const int32_t* indices, int64_t m, int32_t batc
   ConvGeom g;
   int rc = make_geom(&g, batch_size, spatial_shape, ksize, one, pad, dilation);
   if (rc != FSF_OK) return rc;
+  // (kept beside the carve: the ONE query both rulebooks share asks for more than either takes — the strided table is sized from
+  // per_in <= kvol — and the ABI goes on refusing every size it refused before)
   if (workspace_bytes < fsf_rulebook_workspace_bytes(m, g.kvol)) return FSF_ERR_WORKSPACE;
-  FsfArena ar(workspace, workspace_bytes);
   const int64_t cap = (int64_t)pow2_at_least((uint64_t)m * 2);
-  uint64_t* keys = ar.take<uint64_t>(cap);
-  int32_t* vals = ar.take<int32_t>(cap);
-  if (!ar.ok()) return FSF_ERR_WORKSPACE;
-  hipLaunchKernelGGL(hash_fill_empty_kernel, dim3(fsf_stream_grid(cap, 256)), dim3(256), 0, stream, keys, cap);
-  hipLaunchKernelGGL(rb_insert_inputs_kernel, dim3(fsf_stream_grid(m, 256)), dim3(256), 0, stream, indices, m, g, keys,
-                     vals, (uint64_t)(cap - 1));
-  hipLaunchKernelGGL(rb_subm_kernel, dim3(fsf_stream_grid(m * g.kvol, 256)), dim3(256), 0, stream, indices, m, g, keys,
-                     vals, (uint64_t)(cap - 1), nbr);
+  FSF_CARVE(RbSubmLayout, l, workspace, workspace_bytes, cap);
+  hipLaunchKernelGGL(hash_fill_empty_kernel, dim3(fsf_stream_grid(cap, 256)), dim3(256), 0, stream, l.keys, cap);
+  hipLaunchKernelGGL(rb_insert_inputs_kernel, dim3(fsf_stream_grid(m, 256)), dim3(256), 0, stream, indices, m, g, l.keys,
+                     l.vals, (uint64_t)(cap - 1));
+  hipLaunchKernelGGL(rb_subm_kernel, dim3(fsf_stream_grid(m * g.kvol, 256)), dim3(256), 0, stream, indices, m, g, l.keys,
+                     l.vals, (uint64_t)(cap - 1), nbr);
   FSF_LAUNCH_CHECK();
   return FSF_OK;
 }
@@ -413,8 +427,8 @@ extern "C" int fsf_rulebook_strided(const int32_t* indices, int64_t m, int32_t b
     if (m_out_dev) FSF_HIP_TRY(hipMemsetAsync(m_out_dev, 0, sizeof(int64_t), stream));
     return FSF_OK;
   }
+  // (kept beside the carve, as in fsf_rulebook_subm)
   if (workspace_bytes < fsf_rulebook_workspace_bytes(m, g.kvol)) return FSF_ERR_WORKSPACE;
-  FsfArena ar(workspace, workspace_bytes);
   const int64_t in_cap = (int64_t)pow2_at_least((uint64_t)m * 2);
   const int64_t cand = m * g.kvol;
   // distinct output sites one input can propose: per dim, the offsets k with (in + pad - k*dil) % stride == 0
@@ -422,34 +436,24 @@ extern "C" int fsf_rulebook_strided(const int32_t* indices, int64_t m, int32_t b
   const int pz_ = g.sz / gcd(g.sz, g.dz), py_ = g.sy / gcd(g.sy, g.dy), px_ = g.sx / gcd(g.sx, g.dx);
   const int64_t per_in = (int64_t)((g.kz + pz_ - 1) / pz_) * ((g.ky + py_ - 1) / py_) * ((g.kx + px_ - 1) / px_);
   const int64_t set_cap = (int64_t)pow2_at_least((uint64_t)(m * per_in) * 2);
-  // (the two key tables back to back — capacities are powers of two >= 2, so both stay 256-byte aligned: ONE fill launch)
-  uint64_t* in_keys = ar.take<uint64_t>(in_cap + set_cap);
-  uint64_t* set_keys = in_keys + in_cap;
-  int32_t* in_vals = ar.take<int32_t>(in_cap);
-  int32_t* set_vals = ar.take<int32_t>(set_cap);
-  uint64_t* list_a = ar.take<uint64_t>(cand);
-  uint64_t* list_b = ar.take<uint64_t>(cand);
-  uint32_t* lv_a = ar.take<uint32_t>(cand);
-  uint32_t* lv_b = ar.take<uint32_t>(cand);
-  uint32_t* hist = ar.take<uint32_t>((radix_num_tiles(cand) + 1) * RS_BINS);
-  uint32_t* count_dev = ar.take<uint32_t>(1);
-  if (!ar.ok()) return FSF_ERR_WORKSPACE;
+  FSF_CARVE(RbStridedLayout, l, workspace, workspace_bytes, in_cap, set_cap, cand);
+  uint64_t* const set_keys = l.in_keys + in_cap;
 
-  hipLaunchKernelGGL(hash_fill_empty_kernel, dim3(fsf_stream_grid(in_cap + set_cap, 256)), dim3(256), 0, stream, in_keys,
-                     in_cap + set_cap, count_dev);
-  hipLaunchKernelGGL(rb_insert_inputs_kernel, dim3(fsf_stream_grid(m, 256)), dim3(256), 0, stream, indices, m, g, in_keys,
-                     in_vals, (uint64_t)(in_cap - 1));
+  hipLaunchKernelGGL(hash_fill_empty_kernel, dim3(fsf_stream_grid(in_cap + set_cap, 256)), dim3(256), 0, stream, l.in_keys,
+                     in_cap + set_cap, l.count_dev);
+  hipLaunchKernelGGL(rb_insert_inputs_kernel, dim3(fsf_stream_grid(m, 256)), dim3(256), 0, stream, indices, m, g, l.in_keys,
+                     l.in_vals, (uint64_t)(in_cap - 1));
   const bool propose_by_pair = false;  // (the round-1 kernel: only where the per-workgroup list of the rows kernel does not fit)
   // (the per-workgroup list of the rows kernel is 256 * per_in * 8 bytes of dynamic LDS + 8 static: 64 KB without an attribute)
   if (propose_by_pair || 256 * per_in * 8 + 8 > 64 * 1024 || (m + 255) / 256 > 0x7FFFFFFF)
     hipLaunchKernelGGL(rb_propose_kernel, dim3(fsf_stream_grid(cand, 256)), dim3(256), 0, stream, indices, m, g, set_keys,
-                       (uint64_t)(set_cap - 1), list_a, count_dev);
+                       (uint64_t)(set_cap - 1), l.list.keys_a, l.count_dev);
   else
     hipLaunchKernelGGL(rb_propose_rows_kernel, dim3((unsigned)((m + 255) / 256)), dim3(256), (size_t)256 * per_in * 8, stream, indices, m,
-                       g, set_keys, (uint64_t)(set_cap - 1), list_a, count_dev);
+                       g, set_keys, (uint64_t)(set_cap - 1), l.list.keys_a, l.count_dev);
   FSF_LAUNCH_CHECK();
   uint32_t count_h = 0;
-  FSF_READ_BACK(&count_h, count_dev, sizeof(uint32_t), stream);
+  FSF_READ_BACK(&count_h, l.count_dev, sizeof(uint32_t), stream);
   const int64_t m_out = (int64_t)count_h;
   *m_out_host = m_out;
   if (m_out > cap_out) return FSF_ERR_CAPACITY;
@@ -463,20 +467,20 @@ extern "C" int fsf_rulebook_strided(const int32_t* indices, int64_t m, int32_t b
     return FSF_OK;
   }
   // ascending linear (b,z,y,x) order of the output sites
-  hipLaunchKernelGGL(rb_iota_kernel, dim3(fsf_stream_grid(m_out, 256)), dim3(256), 0, stream, lv_a, m_out);
+  hipLaunchKernelGGL(rb_iota_kernel, dim3(fsf_stream_grid(m_out, 256)), dim3(256), 0, stream, l.list.vals_a, m_out);
   const uint64_t total_cells = (uint64_t)g.B * g.OZ * g.OY * g.OX;
   uint64_t* sorted;
   uint32_t* sorted_v;
-  rc = radix_sort_pairs(list_a, lv_a, list_b, lv_b, hist, m_out, bit_width64(total_cells - 1), &sorted, &sorted_v, stream);
+  rc = radix_sort_pairs(l.list.keys_a, l.list.vals_a, l.list.keys_b, l.list.vals_b, l.list.hist, m_out, bit_width64(total_cells - 1), &sorted, &sorted_v, stream);
   if (rc != FSF_OK) return rc;
   // the candidate set's key array already holds exactly the output sites: reuse it as the out-site map
   hipLaunchKernelGGL(rb_assign_out_kernel, dim3(fsf_stream_grid(m_out, 256)), dim3(256), 0, stream, sorted, m_out, g,
-                     out_indices, set_keys, set_vals, (uint64_t)(set_cap - 1));
+                     out_indices, set_keys, l.set_vals, (uint64_t)(set_cap - 1));
   hipLaunchKernelGGL(rb_strided_nbr_kernel, dim3(fsf_stream_grid(m_out * g.kvol, 256)), dim3(256), 0, stream, out_indices,
-                     m_out, g, in_keys, in_vals, (uint64_t)(in_cap - 1), nbr);
+                     m_out, g, l.in_keys, l.in_vals, (uint64_t)(in_cap - 1), nbr);
   if (nbr_inv)
     hipLaunchKernelGGL(rb_strided_inv_kernel, dim3(fsf_stream_grid(cand, 256)), dim3(256), 0, stream, indices, m, g,
-                       set_keys, set_vals, (uint64_t)(set_cap - 1), nbr_inv);
+                       set_keys, l.set_vals, (uint64_t)(set_cap - 1), nbr_inv);
   FSF_LAUNCH_CHECK();
   return FSF_OK;
 }
@@ -535,12 +539,16 @@ __global__ void __launch_bounds__(256) remap_indices_kernel(const int32_t* __res
 }
 }  // namespace fsf
 
+struct MoLayout {
+  RbSubmLayout table;
+  RadixScratch sort;
+  MoLayout(FsfArena& ar, int64_t m, int64_t cap) : table(ar, cap), sort(ar, m) {}
+};
+
 extern "C" int64_t fsf_order_by_neighbor_mask_workspace_bytes(int64_t m) {
   if (m < 0) return 0;
   const int64_t n = m > 0 ? m : 1;
-  const int64_t cap = (int64_t)pow2_at_least((uint64_t)n * 2);
-  return fsf_align_up(cap * 8, 256) + fsf_align_up(cap * 4, 256) + 2 * fsf_align_up(n * 8, 256) + 2 * fsf_align_up(n * 4, 256) +
-         fsf_align_up((radix_num_tiles(n) + 1) * RS_BINS * 4, 256) + 256;
+  return fsf_layout_bytes<MoLayout>(n, (int64_t)pow2_at_least((uint64_t)n * 2));
 }
 
 extern "C" int fsf_order_by_neighbor_mask(const int32_t* indices, int64_t m, int32_t batch_size, const int32_t spatial_shape[3],
@@ -552,25 +560,17 @@ extern "C" int fsf_order_by_neighbor_mask(const int32_t* indices, int64_t m, int
   ConvGeom g;
   int rc = make_geom(&g, batch_size, spatial_shape, three, one, one, one);
   if (rc != FSF_OK) return rc;
-  if (!workspace || workspace_bytes < fsf_order_by_neighbor_mask_workspace_bytes(m)) return FSF_ERR_WORKSPACE;
-  FsfArena ar(workspace, workspace_bytes);
   const int64_t cap = (int64_t)pow2_at_least((uint64_t)m * 2);
-  uint64_t* hkeys = ar.take<uint64_t>(cap);
-  int32_t* hvals = ar.take<int32_t>(cap);
-  uint64_t* keys_a = ar.take<uint64_t>(m);
-  uint64_t* keys_b = ar.take<uint64_t>(m);
-  uint32_t* vals_a = ar.take<uint32_t>(m);
-  uint32_t* vals_b = ar.take<uint32_t>(m);
-  uint32_t* hist = ar.take<uint32_t>((radix_num_tiles(m) + 1) * RS_BINS);
-  if (!ar.ok()) return FSF_ERR_WORKSPACE;
-  hipLaunchKernelGGL(hash_fill_empty_kernel, dim3(fsf_stream_grid(cap, 256)), dim3(256), 0, stream, hkeys, cap);
-  hipLaunchKernelGGL(rb_insert_inputs_kernel, dim3(fsf_stream_grid(m, 256)), dim3(256), 0, stream, indices, m, g, hkeys, hvals,
+  FSF_CARVE(MoLayout, l, workspace, workspace_bytes, m, cap);
+  const RadixScratch& s = l.sort;
+  hipLaunchKernelGGL(hash_fill_empty_kernel, dim3(fsf_stream_grid(cap, 256)), dim3(256), 0, stream, l.table.keys, cap);
+  hipLaunchKernelGGL(rb_insert_inputs_kernel, dim3(fsf_stream_grid(m, 256)), dim3(256), 0, stream, indices, m, g, l.table.keys, l.table.vals,
                      (uint64_t)(cap - 1));
-  hipLaunchKernelGGL(mo_keys_kernel, dim3((unsigned)fsf_stream_grid(m * 32, 256)), dim3(256), 0, stream, indices, m, g, hkeys, hvals,
-                     (uint64_t)(cap - 1), keys_a, vals_a);
+  hipLaunchKernelGGL(mo_keys_kernel, dim3((unsigned)fsf_stream_grid(m * 32, 256)), dim3(256), 0, stream, indices, m, g, l.table.keys, l.table.vals,
+                     (uint64_t)(cap - 1), s.keys_a, s.vals_a);
   uint64_t* keys = nullptr;
   uint32_t* order = nullptr;
-  rc = radix_sort_pairs(keys_a, vals_a, keys_b, vals_b, hist, m, 19, &keys, &order, stream);
+  rc = radix_sort_pairs(s.keys_a, s.vals_a, s.keys_b, s.vals_b, s.hist, m, 19, &keys, &order, stream);
   if (rc != FSF_OK) return rc;
   hipLaunchKernelGGL(mo_finish_kernel, dim3((unsigned)fsf_stream_grid(m, 256)), dim3(256), 0, stream, order, m, perm, inv_perm);
   FSF_LAUNCH_CHECK();

@@ -270,10 +270,19 @@ static inline bool rows_vec4(const float* p, int64_t ld) { return ((uintptr_t)p 
 
 using namespace fsf;
 
+struct SegTargetsLayout {
+  int nblk;
+  float* table;
+  int32_t* partial;
+  SegTargetsLayout(FsfArena& arena, int64_t num_boxes, int64_t n)
+      : nblk(fsf_cdiv(n, SL_BLOCK)), table(arena.take<float>(SL_BOX_WORDS * num_boxes)), partial(arena.take<int32_t>(nblk)) {}
+};
+// (one slice: a function in place of a layout struct, taken from a hand-made arena in the entry)
+static double* seg_loss_layout(FsfArena& arena, int64_t n) { return arena.take<double>(3 * (int64_t)fsf_cdiv(n, SL_BLOCK)); }
+
 extern "C" int64_t fsf_seg_targets_workspace_bytes(int64_t num_boxes, int64_t n) {
   if (num_boxes < 0 || n < 0) return -1;
-  return fsf_align_up((int64_t)sizeof(float) * SL_BOX_WORDS * (num_boxes > 0 ? num_boxes : 1), 256) +
-         fsf_align_up((int64_t)sizeof(int32_t) * (fsf_cdiv(n, SL_BLOCK) > 0 ? fsf_cdiv(n, SL_BLOCK) : 1), 256);
+  return fsf_layout_bytes<SegTargetsLayout>(num_boxes, n);
 }
 
 extern "C" int fsf_seg_targets(const float* points, int64_t n, int64_t pt_stride, const void* batch_idx, int32_t batch_idx_bytes,
@@ -286,34 +295,31 @@ extern "C" int fsf_seg_targets(const float* points, int64_t n, int64_t pt_stride
   if (!count || !box_ptr || (n > 0 && (!points || !batch_idx || !labels || !targets || !mask))) return FSF_ERR_INVALID_ARG;
   if (num_boxes > 0 && (!boxes || !box_labels || box_stride < 7)) return FSF_ERR_INVALID_ARG;
   if (n >= ((int64_t)1 << 40) || num_boxes >= ((int64_t)1 << 31)) return FSF_ERR_UNSUPPORTED;
-  FsfArena arena(workspace, workspace_bytes);
-  float* table = arena.take<float>(SL_BOX_WORDS * num_boxes);
-  const int nblk = fsf_cdiv(n, SL_BLOCK);
-  int32_t* partial = arena.take<int32_t>(nblk);
-  if (!arena.ok()) return FSF_ERR_WORKSPACE;
+  FSF_CARVE(SegTargetsLayout, l, workspace, workspace_bytes, num_boxes, n);
   if (num_boxes > 0) {
     hipLaunchKernelGGL(seg_box_prep_kernel, dim3((unsigned)fsf_cdiv(num_boxes, SL_BLOCK)), dim3(SL_BLOCK), 0, stream, boxes, num_boxes,
-                       box_stride, table);
+                       box_stride, l.table);
     FSF_LAUNCH_CHECK();
   }
-  if (nblk > 0) {
+  if (l.nblk > 0) {
     if (batch_idx_bytes == 8)
-      hipLaunchKernelGGL(seg_targets_kernel<int64_t>, dim3((unsigned)nblk), dim3(SL_BLOCK), 0, stream, points, n, pt_stride,
-                         (const int64_t*)batch_idx, box_ptr, num_samples, table, box_labels, num_classes, labels, targets, mask, partial);
+      hipLaunchKernelGGL(seg_targets_kernel<int64_t>, dim3((unsigned)l.nblk), dim3(SL_BLOCK), 0, stream, points, n, pt_stride,
+                         (const int64_t*)batch_idx, box_ptr, num_samples, l.table, box_labels, num_classes, labels, targets, mask, l.partial);
     else
-      hipLaunchKernelGGL(seg_targets_kernel<int32_t>, dim3((unsigned)nblk), dim3(SL_BLOCK), 0, stream, points, n, pt_stride,
-                         (const int32_t*)batch_idx, box_ptr, num_samples, table, box_labels, num_classes, labels, targets, mask, partial);
+      hipLaunchKernelGGL(seg_targets_kernel<int32_t>, dim3((unsigned)l.nblk), dim3(SL_BLOCK), 0, stream, points, n, pt_stride,
+                         (const int32_t*)batch_idx, box_ptr, num_samples, l.table, box_labels, num_classes, labels, targets, mask, l.partial);
     FSF_LAUNCH_CHECK();
   }
-  hipLaunchKernelGGL(seg_count_final_kernel, dim3(1), dim3(SL_FINAL_BLOCK), 0, stream, partial, (int64_t)nblk, count);
+  hipLaunchKernelGGL(seg_count_final_kernel, dim3(1), dim3(SL_FINAL_BLOCK), 0, stream, l.partial, (int64_t)l.nblk, count);
   FSF_LAUNCH_CHECK();
   return FSF_OK;
 }
 
 extern "C" int64_t fsf_seg_loss_workspace_bytes(int64_t n) {
   if (n < 0) return -1;
-  const int64_t nblk = fsf_cdiv(n, SL_BLOCK);
-  return fsf_align_up((int64_t)sizeof(double) * 3 * (nblk > 0 ? nblk : 1), 256);
+  FsfArena arena = FsfArena::measure();
+  seg_loss_layout(arena, n);
+  return arena.used;
 }
 
 static int seg_loss_check(const float* logits, int64_t ld_logits, const float* votes, int64_t ld_votes, int64_t n, int32_t num_classes,
@@ -334,7 +340,7 @@ extern "C" int fsf_seg_loss_forward(const float* logits, int64_t ld_logits, cons
   if (!loss_ce || !loss_vote || !counts) return FSF_ERR_INVALID_ARG;
   FsfArena arena(workspace, workspace_bytes);
   const int nblk = fsf_cdiv(n, SL_BLOCK);
-  double* partials = arena.take<double>(3 * (int64_t)nblk);
+  double* partials = seg_loss_layout(arena, n);
   if (!arena.ok()) return FSF_ERR_WORKSPACE;
   if (nblk > 0) {
     hipLaunchKernelGGL(seg_loss_partials_kernel, dim3((unsigned)nblk), dim3(SL_BLOCK), 0, stream, logits, ld_logits, votes, ld_votes, n,

@@ -641,10 +641,17 @@ __global__ void __launch_bounds__(256)
 
 using namespace fsf;
 
+struct SegLayout {
+  float* part_val;
+  int32_t* part_arg;
+  SegLayout(FsfArena& ar, int64_t n, int64_t c)
+      : part_val(ar.take<float>(((n + SEG_CHUNK - 1) / SEG_CHUNK + 1) * 2 * c)),
+        part_arg(ar.take<int32_t>(((n + SEG_CHUNK - 1) / SEG_CHUNK + 1) * 2 * c)) {}
+};
+
 extern "C" int64_t fsf_segment_reduce_workspace_bytes(int64_t n, int64_t m, int32_t c) {
   (void)m;
-  const int64_t nchunks = (n + SEG_CHUNK - 1) / SEG_CHUNK + 1;
-  return fsf_align_up(nchunks * 2 * c * 4, 256) * 2 + 256;
+  return fsf_layout_bytes<SegLayout>(n, (int64_t)c);
 }
 
 template <int VEC>
@@ -693,18 +700,15 @@ extern "C" int fsf_segment_reduce(const float* feat, int64_t feat_stride, int64_
       (n > 0 && (!feat || !order || !inv)))
     return FSF_ERR_INVALID_ARG;
   if (m == 0) return FSF_OK;
-  if (workspace_bytes < fsf_segment_reduce_workspace_bytes(n, m, c)) return FSF_ERR_WORKSPACE;
-  FsfArena ar(workspace, workspace_bytes);
-  const int64_t nchunks = (n + SEG_CHUNK - 1) / SEG_CHUNK + 1;
+  FSF_CARVE(SegLayout, l, workspace, workspace_bytes, n, c);
   SegArgs a;
   a.feat = feat; a.order = order; a.inv = inv; a.seg_offsets = seg_offsets; a.out = out;
   a.argmax = (mode == MODE_MAX) ? argmax : nullptr;
-  a.part_val = ar.take<float>(nchunks * 2 * c);
-  a.part_arg = ar.take<int32_t>(nchunks * 2 * c);
+  a.part_val = l.part_val;
+  a.part_arg = l.part_arg;
   a.n = n; a.m = m; a.c = c;
   a.feat_stride = feat_stride > 0 ? feat_stride : c;
   if (a.feat_stride < c) return FSF_ERR_INVALID_ARG;
-  if (!ar.ok()) return FSF_ERR_WORKSPACE;
   const bool vec4 = (c % 4 == 0) && (a.feat_stride % 4 == 0) && (((uintptr_t)feat | (uintptr_t)out) % 16 == 0);
   if (vec4) {
     a.team = pick_team(c, 4);

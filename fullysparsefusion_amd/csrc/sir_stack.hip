@@ -16,7 +16,8 @@
 //
 // Memory: ONE arena from the caller (fsf_sir_stack_arena_bytes): the K21 output of the current block, two row buffers the layers
 // alternate between, two group tables.  The group features land in the caller's [groups, sum of layer widths] table (pre-filled with
-// -inf), the last layer's rows in `rows_out` when the caller wants them.  Nothing is allocated or freed here.
+// -inf), the last layer's rows in `rows_out` when the caller wants them.  Nothing is allocated or freed here.  The size is computed by
+// running the entry's own layout (SstLayout) on a measuring arena.
 #include <algorithm>
 
 #include "common.h"
@@ -45,11 +46,20 @@ static int sst_widths(const FsfSirBlock* blocks, int32_t num_blocks, int64_t* x_
   return FSF_OK;
 }
 
+// xm / cm: the widest K21 output and the widest layer of the stack (sst_widths)
+struct SstLayout {
+  float* xbuf;     // the K21 output of the current block
+  float* rbuf[2];  // the row buffers the layers alternate between
+  float* tbuf[2];  // the group tables
+  SstLayout(FsfArena& ar, int64_t n, int64_t num_groups, int64_t xm, int64_t cm)
+      : xbuf(ar.take<float>(n * xm)), rbuf{ar.take<float>(n * cm), ar.take<float>(n * cm)},
+        tbuf{ar.take<float>(num_groups * cm), ar.take<float>(num_groups * cm)} {}
+};
+
 extern "C" int64_t fsf_sir_stack_arena_bytes(const FsfSirBlock* blocks, int32_t num_blocks, int64_t n, int64_t num_groups) {
   int64_t xm = 0, cm = 0;
   if (!blocks || num_blocks < 1 || n < 0 || num_groups < 0 || sst_widths(blocks, num_blocks, &xm, &cm) != FSF_OK) return 0;
-  const int64_t nn = n > 0 ? n : 1, gg = num_groups > 0 ? num_groups : 1;
-  return fsf_align_up(nn * xm * 4, 256) + 2 * fsf_align_up(nn * cm * 4, 256) + 2 * fsf_align_up(gg * cm * 4, 256) + 256;
+  return fsf_layout_bytes<SstLayout>(n > 0 ? n : 1, num_groups > 0 ? num_groups : 1, xm, cm);
 }
 
 extern "C" int fsf_sir_stack_forward(const FsfSirBlock* blocks, int32_t num_blocks, const float* points, int64_t points_stride, int32_t p_cols,
@@ -60,22 +70,11 @@ extern "C" int fsf_sir_stack_forward(const FsfSirBlock* blocks, int32_t num_bloc
                                      float* groups, int64_t groups_stride, float* rows_out, void* arena, int64_t arena_bytes,
                                      void* stream) {
   if (!blocks || num_blocks < 1 || n < 1 || num_groups < 1 || !points || !f_cluster || !seg_ids || !groups || !arena) return FSF_ERR_INVALID_ARG;
-  if (((uintptr_t)arena & 255) || arena_bytes < fsf_sir_stack_arena_bytes(blocks, num_blocks, n, num_groups)) return FSF_ERR_WORKSPACE;
+  if ((uintptr_t)arena & 255) return FSF_ERR_WORKSPACE;
   int64_t xm = 0, cm = 0;
   int rc = sst_widths(blocks, num_blocks, &xm, &cm);
   if (rc != FSF_OK) return rc;
-  char* base = (char*)arena;
-  float* xbuf = (float*)base;
-  base += fsf_align_up(n * xm * 4, 256);
-  float* rbuf[2];
-  rbuf[0] = (float*)base;
-  base += fsf_align_up(n * cm * 4, 256);
-  rbuf[1] = (float*)base;
-  base += fsf_align_up(n * cm * 4, 256);
-  float* tbuf[2];
-  tbuf[0] = (float*)base;
-  base += fsf_align_up(num_groups * cm * 4, 256);
-  tbuf[1] = (float*)base;
+  FSF_CARVE(SstLayout, l, arena, arena_bytes, n, num_groups, xm, cm);
 
   int64_t col = 0;            // first column of the current layer's group maxima in `groups`
   const float* prev_rows = nullptr;  // the previous block's point rows [n, prev_c] (sorted order)
@@ -105,7 +104,7 @@ extern "C" int fsf_sir_stack_forward(const FsfSirBlock* blocks, int32_t num_bloc
       const FsfSirLayer& L = k.layer[0];
       const bool last_block = b == num_blocks - 1;
       const bool want_rows = k.num_layers > 1 || !last_block || rows_out != nullptr;
-      float* out = !want_rows ? nullptr : (k.num_layers == 1 && last_block ? rows_out : rbuf[rsel]);
+      float* out = !want_rows ? nullptr : (k.num_layers == 1 && last_block ? rows_out : l.rbuf[rsel]);
       const int64_t so_stride = num_groups > 1 ? groups_stride : sst_pad4(L.c);
       rc = fsf_sir_input_linear_segmax(points, points_stride, p_cols, k.xyz_normalizer, b == 0 ? feat_parts : prev_parts,
                                        b == 0 ? feat_strides : prev_strides, b == 0 ? feat_cols : prev_cols, b == 0 ? num_parts : 1,
@@ -122,28 +121,28 @@ extern "C" int fsf_sir_stack_forward(const FsfSirBlock* blocks, int32_t num_bloc
     } else if (b == 0) {
       rc = fsf_sir_input_gather(points, points_stride, p_cols, k.xyz_normalizer, feat_parts, feat_strides, feat_cols, num_parts, feats_index,
                                 direct_parts_mask, extra, extra_stride, e_cols, extra_div, f_cluster, f_cluster_stride, r_cols, k.rel_div, k.w1,
-                                k.g1, k.b1, k.h1, k.w2, k.g2, k.b2, k.h2, k.w3, k.g3, k.b3, k.mlp_eps, k.mlp_act, n, xbuf, cpad, stream);
+                                k.g1, k.b1, k.h1, k.w2, k.g2, k.b2, k.h2, k.w3, k.g3, k.b3, k.mlp_eps, k.mlp_act, n, l.xbuf, cpad, stream);
     } else {
       rc = fsf_sir_input_gather(points, points_stride, p_cols, k.xyz_normalizer, prev_parts, prev_strides, prev_cols, 1, nullptr, 0, extra, extra_stride, e_cols,
                                 extra_div, f_cluster, f_cluster_stride, r_cols, k.rel_div, k.w1, k.g1, k.b1, k.h1, k.w2, k.g2, k.b2, k.h2, k.w3,
-                                k.g3, k.b3, k.mlp_eps, k.mlp_act, n, xbuf, cpad, stream);
+                                k.g3, k.b3, k.mlp_eps, k.mlp_act, n, l.xbuf, cpad, stream);
     }
     if (rc != FSF_OK) return rc;
     // ---- the block's DynamicVFELayers (sst_ops.sorted_stack_forward)
-    const float* x = xbuf;
+    const float* x = l.xbuf;
     int64_t x_stride = cpad;
     int32_t x_cols = k.in_cols;
     for (int i = 0; i < k.num_layers; ++i) {
       const FsfSirLayer& L = k.layer[i];
       const bool last_layer = i == k.num_layers - 1, last_block = b == num_blocks - 1;
       const bool want_rows = !last_layer || !last_block || rows_out != nullptr;
-      float* out = !want_rows ? nullptr : (last_layer && last_block ? rows_out : rbuf[rsel]);
+      float* out = !want_rows ? nullptr : (last_layer && last_block ? rows_out : l.rbuf[rsel]);
       float* seg_out = groups + col;
       const float* table = nullptr;
       const bool done = i == 0 && fused;  // (layer 0 ran in the fused launch, into the same `out` and `seg_out`)
       if (i > 0) {  // (group W_right^T): the right half of cat([point, group[inv]], 1) W^T, once per group
         const float* g = groups + (col - x_cols);
-        float* t = tbuf[tsel];
+        float* t = l.tbuf[tsel];
         tsel ^= 1;
         if (L.right_f16)
           rc = fsf_linear_f16w_norm_act_grouped(g, num_groups, x_cols, groups_stride, L.planes_right, L.c, nullptr, nullptr, nullptr, 0, 0, nullptr,

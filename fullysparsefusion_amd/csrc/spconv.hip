@@ -650,9 +650,16 @@ static SpconvPlan spconv_plan(int64_t m_out, int cin, int cout, int kvol) {
   return p;
 }
 
-static int64_t spconv_queue_bytes(int64_t tiles, int cout_blocks, int ksplit) {
-  return fsf_align_up((SC_NXCD + (ksplit > 1 ? tiles * cout_blocks : 0)) * (int64_t)sizeof(int), 256);
-}
+// workspace = [ksplit partial tiles][work-queue counters]
+struct SpconvLayout {
+  float* partial;  // only with ksplit > 1
+  int64_t queue_at;
+  int* queue;
+  int64_t queue_bytes;  // the whole slice: what the persistent path clears
+  SpconvLayout(FsfArena& ar, const SpconvPlan& p, int64_t m_out, int cout)
+      : partial(p.ksplit > 1 ? ar.take<float>((int64_t)p.ksplit * m_out * cout) : nullptr), queue_at(ar.offset()),
+        queue(ar.take<int>(SC_NXCD + (p.ksplit > 1 ? p.tiles * p.cout_blocks : 0))), queue_bytes(ar.offset() - queue_at) {}
+};
 
 }  // namespace fsf
 
@@ -670,9 +677,7 @@ extern "C" int fsf_spconv_transpose_weight(const float* weight, int32_t kvol, in
 
 extern "C" int64_t fsf_spconv_workspace_bytes(int64_t m_out, int32_t cin, int32_t cout, int32_t kvol) {
   if (m_out <= 0 || cin < 1 || cout < 1 || kvol < 1) return 256;
-  const SpconvPlan p = spconv_plan(m_out, cin, cout, kvol);
-  return (p.ksplit > 1 ? fsf_align_up((int64_t)p.ksplit * m_out * cout * 4, 256) : 0) +
-         spconv_queue_bytes(p.tiles, p.cout_blocks, p.ksplit);
+  return fsf_layout_bytes<SpconvLayout>(spconv_plan(m_out, cin, cout, kvol), m_out, (int)cout);
 }
 
 extern "C" int fsf_spconv_forward(const float* feat, int64_t m_in, int32_t cin, const float* weight_t, int32_t kvol,
@@ -689,19 +694,16 @@ extern "C" int fsf_spconv_forward(const float* feat, int64_t m_in, int32_t cin, 
   const SpconvPlan plan = spconv_plan(m_out, cin, cout, kvol);
   if (plan.tiles >= (int64_t)1 << 31) return FSF_ERR_UNSUPPORTED;
   const int ksplit = plan.ksplit;
-  if (workspace_bytes < fsf_spconv_workspace_bytes(m_out, cin, cout, kvol)) return FSF_ERR_WORKSPACE;
-  if (!workspace) return FSF_ERR_WORKSPACE;
+  FSF_CARVE(SpconvLayout, l, workspace, workspace_bytes, plan, m_out, cout);
   const bool fast = (cin % SC_KC) == 0;
-  // workspace = [ksplit partial tiles][work-queue counters]
-  int* queue = reinterpret_cast<int*>((char*)workspace + (ksplit > 1 ? fsf_align_up((int64_t)ksplit * m_out * cout * 4, 256) : 0));
-  SpconvArgs a{feat, weight_t, nbr, scale, shift, residual, out, (float*)workspace, m_in, m_out,
-               (int)cin, (int)cout, (int)kvol, (int)relu, ksplit, queue, (int)plan.tiles, plan.cout_blocks};
+  SpconvArgs a{feat, weight_t, nbr, scale, shift, residual, out, l.partial, m_in, m_out,
+               (int)cin, (int)cout, (int)kvol, (int)relu, ksplit, l.queue, (int)plan.tiles, plan.cout_blocks};
   dim3 grid((unsigned)plan.tiles, plan.cout_blocks, ksplit);
   if (fast) {  // persistent: one workgroup per resident slot
     const int64_t items = plan.tiles * plan.cout_blocks * ksplit;
     const int64_t slots = plan.tm == 128 ? 256 : 512;
     grid = dim3((unsigned)(items < slots ? items : slots), 1, 1);
-    FSF_HIP_TRY(hipMemsetAsync(queue, 0, spconv_queue_bytes(plan.tiles, plan.cout_blocks, ksplit), stream));
+    FSF_HIP_TRY(hipMemsetAsync(l.queue, 0, (size_t)l.queue_bytes, stream));
   }
 #define FSF_SPCONV_LAUNCH(KERNEL, SMEM_T, NTHREADS)                                                                            \
   do {                                                                                                               \

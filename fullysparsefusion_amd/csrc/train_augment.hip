@@ -203,7 +203,7 @@ extern "C" int fsf_train_augment_points(const float* points, int64_t n_rows, int
   if (n_rows < 0 || cols < 3 || cols > 64 || (n_rows > 0 && (!points || !out)) || !count_dev || !desc) return FSF_ERR_INVALID_ARG;
   if (n_rows >= ((int64_t)1 << 31)) return FSF_ERR_UNSUPPORTED;
   if (!(desc[2] > 0.0f)) return FSF_ERR_INVALID_ARG;
-  if (!workspace || workspace_bytes < fsf_train_augment_points_workspace_bytes(n_rows)) return FSF_ERR_WORKSPACE;
+  FSF_CARVE(RadixScratch, s, workspace, workspace_bytes, n_rows);  // (the sort's scratch is all this entry takes: the query is radix_sort_scratch_bytes)
   TaPointArgs a;
   ta_fill_desc(a.d, desc);
   a.use_range = pc_range ? 1 : 0;
@@ -213,20 +213,13 @@ extern "C" int fsf_train_augment_points(const float* points, int64_t n_rows, int
   a.seed_hi = (uint32_t)((uint64_t)shuffle_seed >> 32);
   FSF_HIP_TRY(hipMemsetAsync(count_dev, 0, sizeof(int64_t), stream));
   if (n_rows > 0) {
-    FsfArena arena(workspace, workspace_bytes);
-    uint64_t* keys_a = arena.take<uint64_t>(n_rows);
-    uint64_t* keys_b = arena.take<uint64_t>(n_rows);
-    uint32_t* vals_a = arena.take<uint32_t>(n_rows);
-    uint32_t* vals_b = arena.take<uint32_t>(n_rows);
-    uint32_t* hist = arena.take<uint32_t>((radix_num_tiles(n_rows) + 1) * RS_BINS);
-    if (!arena.ok()) return FSF_ERR_WORKSPACE;
     const int grid = fsf_stream_grid(n_rows, 256);
-    hipLaunchKernelGGL(train_aug_keys_kernel, dim3(grid), dim3(256), 0, stream, points, n_rows, (int)cols, a, keys_a, vals_a,
+    hipLaunchKernelGGL(train_aug_keys_kernel, dim3(grid), dim3(256), 0, stream, points, n_rows, (int)cols, a, s.keys_a, s.vals_a,
                        reinterpret_cast<unsigned long long*>(count_dev));
     FSF_LAUNCH_CHECK();
     uint64_t* keys_sorted = nullptr;
     uint32_t* vals_sorted = nullptr;
-    const int rc = radix_sort_pairs(keys_a, vals_a, keys_b, vals_b, hist, n_rows, a.shuffle ? 32 : 1, &keys_sorted, &vals_sorted, stream);
+    const int rc = radix_sort_pairs(s.keys_a, s.vals_a, s.keys_b, s.vals_b, s.hist, n_rows, a.shuffle ? 32 : 1, &keys_sorted, &vals_sorted, stream);
     if (rc != FSF_OK) return rc;
     const bool vec = cols % 4 == 0 && ((uintptr_t)points % 16) == 0 && ((uintptr_t)out % 16) == 0;
     if (vec)

@@ -206,7 +206,6 @@ struct IgIn {
   __device__ uint32_t operator()(int64_t i) const { return (i == 0 || keys[i] != keys[i - 1]) ? 1u : 0u; }
 };
 
-
 // ---- K25: which cluster voxels (and which (group, point) pairs) survive ClusterAssigner's density filter ------------------------
 // ClusterAssigner.forward_single_class (single_stage_fsd.py:951-956) per class group: a voxel key with fewer than `min_points` pairs
 // is dropped — unless NONE of the group's keys is dense enough, then the group keeps everything.  With all groups in one key list
@@ -330,9 +329,23 @@ struct GpOut {
 
 using namespace fsf;
 
+struct UqLayout {
+  RadixScratch sort;
+  // [sort.hist | tile_sums | err_flag (+ the read-back pair)] are consecutive: ONE memset clears what the sort, the scan and the packing
+  // kernel each used to clear for themselves
+  uint32_t* tile_sums;
+  int32_t* err_flag;
+  size_t zero_bytes;  // sort.hist up to here
+  int64_t* ret_dev;
+  ColRange* range_dev;
+  UqLayout(FsfArena& ar, int64_t n)
+      : sort(ar, n), tile_sums(ar.take<uint32_t>(scan_num_tiles(n))), err_flag(ar.take<int32_t>(1)),
+        zero_bytes((size_t)(ar.offset() - sort.hist_at)), ret_dev(ar.take<int64_t>(2)), range_dev(ar.take<ColRange>(1)) {}
+};
+
 extern "C" int64_t fsf_unique_rows_workspace_bytes(int64_t n, int32_t k) {
   (void)k;
-  return radix_sort_scratch_bytes(n) + fsf_align_up(scan_num_tiles(n) * 4, 256) + 4 * 256;
+  return fsf_layout_bytes<UqLayout>(n);
 }
 
 extern "C" int fsf_unique_rows(const int64_t* coors, int64_t n, int32_t k, const int64_t* col_min,
@@ -353,20 +366,7 @@ extern "C" int fsf_unique_rows(const int64_t* coors, int64_t n, int32_t k, const
     }
     return FSF_OK;
   }
-  FsfArena ar(workspace, workspace_bytes);
-  uint64_t* keys_a = ar.take<uint64_t>(n);
-  uint64_t* keys_b = ar.take<uint64_t>(n);
-  uint32_t* vals_a = ar.take<uint32_t>(n);
-  uint32_t* vals_b = ar.take<uint32_t>(n);
-  // [hist | tile_sums | err_flag (+ the read-back pair)] are consecutive: ONE memset clears what the sort, the scan and the packing
-  // kernel each used to clear for themselves
-  uint32_t* hist = ar.take<uint32_t>((radix_num_tiles(n) + 1) * RS_BINS);
-  uint32_t* tile_sums = ar.take<uint32_t>(scan_num_tiles(n));
-  int32_t* err_flag = ar.take<int32_t>(1);
-  int64_t* ret_dev = ar.take<int64_t>(2);
-  const size_t zero_bytes = (size_t)((char*)ret_dev - (char*)hist);
-  ColRange* range_dev = ar.take<ColRange>(1);
-  if (!ar.ok()) return FSF_ERR_WORKSPACE;
+  FSF_CARVE(UqLayout, l, workspace, workspace_bytes, n);
 
   const int grid = fsf_stream_grid(n, 256);
   const int rgrid = grid > 512 ? 512 : grid;  // one atomic pair per column per workgroup
@@ -379,14 +379,14 @@ extern "C" int fsf_unique_rows(const int64_t* coors, int64_t n, int32_t k, const
     }
   } else {
     // data-dependent bounds: one small D2H copy + sync (torch.unique in the reference syncs as well)
-    hipLaunchKernelGGL(uq_range_init_kernel, dim3(1), dim3(64), 0, stream, range_dev);
+    hipLaunchKernelGGL(uq_range_init_kernel, dim3(1), dim3(64), 0, stream, l.range_dev);
     switch (k) {
-      case 1: hipLaunchKernelGGL((uq_range_kernel<1>), dim3(rgrid), dim3(256), 0, stream, coors, n, range_dev); break;
-      case 2: hipLaunchKernelGGL((uq_range_kernel<2>), dim3(rgrid), dim3(256), 0, stream, coors, n, range_dev); break;
-      case 3: hipLaunchKernelGGL((uq_range_kernel<3>), dim3(rgrid), dim3(256), 0, stream, coors, n, range_dev); break;
-      default: hipLaunchKernelGGL((uq_range_kernel<4>), dim3(rgrid), dim3(256), 0, stream, coors, n, range_dev); break;
+      case 1: hipLaunchKernelGGL((uq_range_kernel<1>), dim3(rgrid), dim3(256), 0, stream, coors, n, l.range_dev); break;
+      case 2: hipLaunchKernelGGL((uq_range_kernel<2>), dim3(rgrid), dim3(256), 0, stream, coors, n, l.range_dev); break;
+      case 3: hipLaunchKernelGGL((uq_range_kernel<3>), dim3(rgrid), dim3(256), 0, stream, coors, n, l.range_dev); break;
+      default: hipLaunchKernelGGL((uq_range_kernel<4>), dim3(rgrid), dim3(256), 0, stream, coors, n, l.range_dev); break;
     }
-    FSF_READ_BACK(&range, range_dev, sizeof(ColRange), stream);
+    FSF_READ_BACK(&range, l.range_dev, sizeof(ColRange), stream);
   }
   PackSpec spec;
   spec.k = k;
@@ -412,35 +412,41 @@ extern "C" int fsf_unique_rows(const int64_t* coors, int64_t n, int32_t k, const
     spec.mask[j] = bits[j] >= 64 ? ~0ull : ((1ull << bits[j]) - 1ull);
     sh += bits[j];
   }
-  FSF_HIP_TRY(hipMemsetAsync(hist, 0, zero_bytes, stream));
+  FSF_HIP_TRY(hipMemsetAsync(l.sort.hist, 0, l.zero_bytes, stream));
   switch (k) {
-    case 1: hipLaunchKernelGGL((uq_pack_kernel<1>), dim3(grid), dim3(256), 0, stream, coors, n, spec, keys_a, vals_a, err_flag); break;
-    case 2: hipLaunchKernelGGL((uq_pack_kernel<2>), dim3(grid), dim3(256), 0, stream, coors, n, spec, keys_a, vals_a, err_flag); break;
-    case 3: hipLaunchKernelGGL((uq_pack_kernel<3>), dim3(grid), dim3(256), 0, stream, coors, n, spec, keys_a, vals_a, err_flag); break;
-    default: hipLaunchKernelGGL((uq_pack_kernel<4>), dim3(grid), dim3(256), 0, stream, coors, n, spec, keys_a, vals_a, err_flag); break;
+    case 1: hipLaunchKernelGGL((uq_pack_kernel<1>), dim3(grid), dim3(256), 0, stream, coors, n, spec, l.sort.keys_a, l.sort.vals_a, l.err_flag); break;
+    case 2: hipLaunchKernelGGL((uq_pack_kernel<2>), dim3(grid), dim3(256), 0, stream, coors, n, spec, l.sort.keys_a, l.sort.vals_a, l.err_flag); break;
+    case 3: hipLaunchKernelGGL((uq_pack_kernel<3>), dim3(grid), dim3(256), 0, stream, coors, n, spec, l.sort.keys_a, l.sort.vals_a, l.err_flag); break;
+    default: hipLaunchKernelGGL((uq_pack_kernel<4>), dim3(grid), dim3(256), 0, stream, coors, n, spec, l.sort.keys_a, l.sort.vals_a, l.err_flag); break;
   }
   uint64_t* keys_s;
   uint32_t* vals_s;
-  int rc = radix_sort_pairs(keys_a, vals_a, keys_b, vals_b, hist, n, total_bits, &keys_s, &vals_s, stream, true);
+  int rc = radix_sort_pairs(l.sort.keys_a, l.sort.vals_a, l.sort.keys_b, l.sort.vals_b, l.sort.hist, n, total_bits, &keys_s, &vals_s, stream, true);
   if (rc != FSF_OK) return rc;
   HeadIn hin{keys_s};
   HeadOut hout{keys_s, vals_s, spec, new_coors, inv, order, seg_offsets};
-  rc = exclusive_scan_u32(hin, hout, n, tile_sums, nullptr, m_dev, stream, 1, true);
+  rc = exclusive_scan_u32(hin, hout, n, l.tile_sums, nullptr, m_dev, stream, 1, true);
   if (rc != FSF_OK) return rc;
-  hipLaunchKernelGGL(uq_finish_kernel, dim3(grid), dim3(256), 0, stream, m_dev, n, seg_offsets, cnt, err_flag, m_host ? ret_dev : nullptr);
+  hipLaunchKernelGGL(uq_finish_kernel, dim3(grid), dim3(256), 0, stream, m_dev, n, seg_offsets, cnt, l.err_flag, m_host ? l.ret_dev : nullptr);
   FSF_LAUNCH_CHECK();
   if (m_host) {
     int64_t ret_h[2] = {0, 0};
-    FSF_READ_BACK(ret_h, ret_dev, sizeof(ret_h), stream);  // (count + error flag in one copy)
+    FSF_READ_BACK(ret_h, l.ret_dev, sizeof(ret_h), stream);  // (count + error flag in one copy)
     *m_host = ret_h[0];
     if (ret_h[1]) return FSF_ERR_KEY_RANGE;
   }
   return FSF_OK;
 }
 
+struct SpLayout {
+  RadixScratch sort;
+  int32_t* err_flag;
+  SpLayout(FsfArena& ar, int64_t n) : sort(ar, n), err_flag(ar.take<int32_t>(1)) {}
+};
+
 extern "C" int64_t fsf_segment_plan_workspace_bytes(int64_t n, int64_t m) {
   (void)m;
-  return radix_sort_scratch_bytes(n) + 2 * 256;
+  return fsf_layout_bytes<SpLayout>(n);
 }
 
 extern "C" int fsf_segment_plan_from_inverse(const int64_t* inv, int64_t n, int64_t m, int32_t* order,
@@ -449,22 +455,15 @@ extern "C" int fsf_segment_plan_from_inverse(const int64_t* inv, int64_t n, int6
   hipStream_t stream = (hipStream_t)stream_;
   if (n < 0 || m < 0 || !seg_offsets || (n > 0 && (!inv || !order))) return FSF_ERR_INVALID_ARG;
   if (n >= (int64_t)1 << 31 || m >= (int64_t)1 << 31) return FSF_ERR_UNSUPPORTED;
-  if (workspace_bytes < fsf_segment_plan_workspace_bytes(n, m)) return FSF_ERR_WORKSPACE;
-  FsfArena ar(workspace, workspace_bytes);
-  uint64_t* keys_a = ar.take<uint64_t>(n);
-  uint64_t* keys_b = ar.take<uint64_t>(n);
-  uint32_t* vals_a = ar.take<uint32_t>(n);
-  uint32_t* vals_b = ar.take<uint32_t>(n);
-  uint32_t* hist = ar.take<uint32_t>((radix_num_tiles(n) + 1) * RS_BINS);
-  int32_t* err_flag = ar.take<int32_t>(1);
-  if (!ar.ok()) return FSF_ERR_WORKSPACE;
+  FSF_CARVE(SpLayout, l, workspace, workspace_bytes, n);
+  const RadixScratch& s = l.sort;
   const int grid = fsf_stream_grid(n + 1, 256);
-  FSF_HIP_TRY(hipMemsetAsync(err_flag, 0, sizeof(int32_t), stream));
-  uint64_t* keys_s = keys_a;
-  uint32_t* vals_s = vals_a;
+  FSF_HIP_TRY(hipMemsetAsync(l.err_flag, 0, sizeof(int32_t), stream));
+  uint64_t* keys_s = s.keys_a;
+  uint32_t* vals_s = s.vals_a;
   if (n > 0) {
-    hipLaunchKernelGGL(sp_pack_kernel, dim3(grid), dim3(256), 0, stream, inv, n, m, keys_a, vals_a, err_flag);
-    int rc = radix_sort_pairs(keys_a, vals_a, keys_b, vals_b, hist, n, bit_width_u64(m > 0 ? (uint64_t)(m - 1) : 0),
+    hipLaunchKernelGGL(sp_pack_kernel, dim3(grid), dim3(256), 0, stream, inv, n, m, s.keys_a, s.vals_a, l.err_flag);
+    int rc = radix_sort_pairs(s.keys_a, s.vals_a, s.keys_b, s.vals_b, s.hist, n, bit_width_u64(m > 0 ? (uint64_t)(m - 1) : 0),
                               &keys_s, &vals_s, stream);
     if (rc != FSF_OK) return rc;
   }
@@ -475,10 +474,18 @@ extern "C" int fsf_segment_plan_from_inverse(const int64_t* inv, int64_t n, int6
   return FSF_OK;
 }
 
-extern "C" int64_t fsf_ingroup_rank_workspace_bytes(int64_t n) {
-  return radix_sort_scratch_bytes(n) + fsf_align_up(scan_num_tiles(n) * 4, 256) + fsf_align_up((n > 0 ? n : 1) * 4, 256) +
-         4 * 256;
-}
+struct IgLayout {
+  RadixScratch sort;
+  uint32_t* tile_sums;
+  int32_t* seg_start;
+  ColRange* range_dev;
+  int32_t* err_flag;
+  IgLayout(FsfArena& ar, int64_t n)
+      : sort(ar, n), tile_sums(ar.take<uint32_t>(scan_num_tiles(n))), seg_start(ar.take<int32_t>(n)), range_dev(ar.take<ColRange>(1)),
+        err_flag(ar.take<int32_t>(1)) {}
+};
+
+extern "C" int64_t fsf_ingroup_rank_workspace_bytes(int64_t n) { return fsf_layout_bytes<IgLayout>(n); }
 
 namespace fsf {
 // head position of each sorted element = running max of (head ? i : 0): computed by a scan of head flags
@@ -506,23 +513,13 @@ extern "C" int fsf_ingroup_rank(const int64_t* group_inds, int64_t n, int64_t* o
   if (n < 0 || (n > 0 && (!group_inds || !out_inds))) return FSF_ERR_INVALID_ARG;
   if (n == 0) return FSF_OK;
   if (n >= (int64_t)1 << 31) return FSF_ERR_UNSUPPORTED;
-  if (workspace_bytes < fsf_ingroup_rank_workspace_bytes(n)) return FSF_ERR_WORKSPACE;
-  FsfArena ar(workspace, workspace_bytes);
-  uint64_t* keys_a = ar.take<uint64_t>(n);
-  uint64_t* keys_b = ar.take<uint64_t>(n);
-  uint32_t* vals_a = ar.take<uint32_t>(n);
-  uint32_t* vals_b = ar.take<uint32_t>(n);
-  uint32_t* hist = ar.take<uint32_t>((radix_num_tiles(n) + 1) * RS_BINS);
-  uint32_t* tile_sums = ar.take<uint32_t>(scan_num_tiles(n));
-  int32_t* seg_start = ar.take<int32_t>(n);
-  ColRange* range_dev = ar.take<ColRange>(1);
-  int32_t* err_flag = ar.take<int32_t>(1);
-  if (!ar.ok()) return FSF_ERR_WORKSPACE;
+  FSF_CARVE(IgLayout, l, workspace, workspace_bytes, n);
+  const RadixScratch& s = l.sort;
   const int grid = fsf_stream_grid(n, 256);
   ColRange range;
-  hipLaunchKernelGGL(uq_range_init_kernel, dim3(1), dim3(64), 0, stream, range_dev);
-  hipLaunchKernelGGL((uq_range_kernel<1>), dim3(grid > 512 ? 512 : grid), dim3(256), 0, stream, group_inds, n, range_dev);
-  FSF_READ_BACK(&range, range_dev, sizeof(ColRange), stream);
+  hipLaunchKernelGGL(uq_range_init_kernel, dim3(1), dim3(64), 0, stream, l.range_dev);
+  hipLaunchKernelGGL((uq_range_kernel<1>), dim3(grid > 512 ? 512 : grid), dim3(256), 0, stream, group_inds, n, l.range_dev);
+  FSF_READ_BACK(&range, l.range_dev, sizeof(ColRange), stream);
   PackSpec spec;
   for (int j = 0; j < 4; ++j) {
     spec.mn[j] = 0; spec.mx[j] = 0; spec.shift[j] = 0; spec.mask[j] = 0;
@@ -532,26 +529,37 @@ extern "C" int fsf_ingroup_rank(const int64_t* group_inds, int64_t n, int64_t* o
   spec.mx[0] = range.mx[0];
   const int bits = bit_width_u64((uint64_t)range.mx[0] - (uint64_t)range.mn[0]);
   spec.mask[0] = bits >= 64 ? ~0ull : ((1ull << bits) - 1ull);
-  FSF_HIP_TRY(hipMemsetAsync(err_flag, 0, sizeof(int32_t), stream));
-  hipLaunchKernelGGL((uq_pack_kernel<1>), dim3(grid), dim3(256), 0, stream, group_inds, n, spec, keys_a, vals_a, err_flag);
+  FSF_HIP_TRY(hipMemsetAsync(l.err_flag, 0, sizeof(int32_t), stream));
+  hipLaunchKernelGGL((uq_pack_kernel<1>), dim3(grid), dim3(256), 0, stream, group_inds, n, spec, s.keys_a, s.vals_a, l.err_flag);
   uint64_t* keys_s;
   uint32_t* vals_s;
-  int rc = radix_sort_pairs(keys_a, vals_a, keys_b, vals_b, hist, n, bits, &keys_s, &vals_s, stream);
+  int rc = radix_sort_pairs(s.keys_a, s.vals_a, s.keys_b, s.vals_b, s.hist, n, bits, &keys_s, &vals_s, stream);
   if (rc != FSF_OK) return rc;
   // seg_of aliases the no-longer-needed alternate value buffer
-  int32_t* seg_of = (int32_t*)(vals_s == vals_a ? vals_b : vals_a);
+  int32_t* seg_of = (int32_t*)(vals_s == s.vals_a ? s.vals_b : s.vals_a);
   IgIn iin{keys_s};
-  IgOut iout{seg_start, seg_of};
-  rc = exclusive_scan_u32(iin, iout, n, tile_sums, nullptr, nullptr, stream);
+  IgOut iout{l.seg_start, seg_of};
+  rc = exclusive_scan_u32(iin, iout, n, l.tile_sums, nullptr, nullptr, stream);
   if (rc != FSF_OK) return rc;
-  hipLaunchKernelGGL(ig_final_kernel, dim3(grid), dim3(256), 0, stream, vals_s, seg_of, seg_start, n, out_inds);
+  hipLaunchKernelGGL(ig_final_kernel, dim3(grid), dim3(256), 0, stream, vals_s, seg_of, l.seg_start, n, out_inds);
   FSF_LAUNCH_CHECK();
   return FSF_OK;
 }
 
-extern "C" int64_t fsf_cluster_key_survival_workspace_bytes(int64_t m, int64_t n) {
-  return fsf_align_up((m > 0 ? m : 1) * 4, 256) + fsf_align_up(scan_num_tiles(m) * 4, 256) + fsf_align_up(scan_num_tiles(n) * 4, 256) + 6 * 256;
-}
+struct KsLayout {
+  int32_t* kpos;
+  // [has_valid | tile sums of the two scans] are consecutive: one memset
+  int64_t zero_at;
+  int* has_valid;
+  uint32_t *tiles_k, *tiles_p;
+  size_t zero_bytes;
+  int64_t* totals;
+  KsLayout(FsfArena& ar, int64_t m, int64_t n)
+      : kpos(ar.take<int32_t>(m)), zero_at(ar.offset()), has_valid(ar.take<int>(64)), tiles_k(ar.take<uint32_t>(scan_num_tiles(m))),
+        tiles_p(ar.take<uint32_t>(scan_num_tiles(n))), zero_bytes((size_t)(ar.offset() - zero_at)), totals(ar.take<int64_t>(2)) {}
+};
+
+extern "C" int64_t fsf_cluster_key_survival_workspace_bytes(int64_t m, int64_t n) { return fsf_layout_bytes<KsLayout>(m, n); }
 
 extern "C" int fsf_cluster_key_survival(const int64_t* new_keys, int32_t key_cols, const int64_t* cnt, int64_t m, const int64_t* inv,
                                         int64_t n, int64_t batch_size, int64_t min_points, int32_t num_groups, int64_t* k_idx,
@@ -562,28 +570,19 @@ extern "C" int fsf_cluster_key_survival(const int64_t* new_keys, int32_t key_col
       (m > 0 && (!new_keys || !cnt || !k_idx)) || (n > 0 && (!inv || !v_idx || !vox_inv)))
     return FSF_ERR_INVALID_ARG;
   if (m >= ((int64_t)1 << 31) || n >= ((int64_t)1 << 31)) return FSF_ERR_UNSUPPORTED;
-  if (workspace_bytes < fsf_cluster_key_survival_workspace_bytes(m, n) || !workspace) return FSF_ERR_WORKSPACE;
+  FSF_CARVE(KsLayout, l, workspace, workspace_bytes, m, n);
   counts_host[0] = counts_host[1] = 0;
   if (m == 0 || n == 0) return FSF_OK;
-  FsfArena ar(workspace, workspace_bytes);
-  int32_t* kpos = ar.take<int32_t>(m);
-  // [has_valid | tile sums of the two scans] are consecutive: one memset
-  int* has_valid = ar.take<int>(64);
-  uint32_t* tiles_k = ar.take<uint32_t>(scan_num_tiles(m));
-  uint32_t* tiles_p = ar.take<uint32_t>(scan_num_tiles(n));
-  int64_t* totals = ar.take<int64_t>(2);
-  const size_t zero_bytes = (size_t)((char*)totals - (char*)has_valid);
-  if (!ar.ok()) return FSF_ERR_WORKSPACE;
-  FSF_HIP_TRY(hipMemsetAsync(has_valid, 0, zero_bytes, stream));
+  FSF_HIP_TRY(hipMemsetAsync(l.has_valid, 0, l.zero_bytes, stream));
   hipLaunchKernelGGL(ks_group_valid_kernel, dim3(fsf_stream_grid(m, 256)), dim3(256), 0, stream, new_keys, (int)key_cols, cnt, m,
-                     batch_size, min_points, (int)num_groups, has_valid);
-  int rc = exclusive_scan_u32(KsKeyIn{new_keys, (int)key_cols, cnt, batch_size, min_points, (int)num_groups, has_valid},
-                              KsKeyOut{k_idx, kpos, k_group, new_keys, (int)key_cols, batch_size}, m, tiles_k, nullptr, totals, stream, 1, true);
+                     batch_size, min_points, (int)num_groups, l.has_valid);
+  int rc = exclusive_scan_u32(KsKeyIn{new_keys, (int)key_cols, cnt, batch_size, min_points, (int)num_groups, l.has_valid},
+                              KsKeyOut{k_idx, l.kpos, k_group, new_keys, (int)key_cols, batch_size}, m, l.tiles_k, nullptr, l.totals, stream, 1, true);
   if (rc != FSF_OK) return rc;
-  rc = exclusive_scan_u32(KsPairIn{inv, kpos}, KsPairOut{inv, kpos, v_idx, vox_inv}, n, tiles_p, nullptr, totals + 1, stream, 1, true);
+  rc = exclusive_scan_u32(KsPairIn{inv, l.kpos}, KsPairOut{inv, l.kpos, v_idx, vox_inv}, n, l.tiles_p, nullptr, l.totals + 1, stream, 1, true);
   if (rc != FSF_OK) return rc;
   int64_t ret_h[2] = {0, 0};
-  FSF_READ_BACK(ret_h, totals, sizeof(ret_h), stream);  // (both counts in one copy)
+  FSF_READ_BACK(ret_h, l.totals, sizeof(ret_h), stream);  // (both counts in one copy)
   counts_host[0] = ret_h[0];
   counts_host[1] = ret_h[1];
   return FSF_OK;
@@ -606,8 +605,19 @@ extern "C" int fsf_cluster_point_ids(const int32_t* labels, const int32_t* vox_g
   return FSF_OK;
 }
 
+struct GpLayout {
+  int64_t zero_at;
+  uint32_t* any_mask;  // [any_mask | the scan's tile words]: one memset
+  uint32_t* tiles;
+  size_t zero_bytes;
+  int64_t* total;
+  GpLayout(FsfArena& ar, int64_t pairs)
+      : zero_at(ar.offset()), any_mask(ar.take<uint32_t>(1)), tiles(ar.take<uint32_t>(scan_num_tiles(pairs))),
+        zero_bytes((size_t)(ar.offset() - zero_at)), total(ar.take<int64_t>(1)) {}
+};
+
 extern "C" int64_t fsf_group_pairs_workspace_bytes(int64_t n, int32_t ng) {
-  return fsf_align_up(scan_num_tiles((n > 0 ? n : 1) * (ng > 0 ? ng : 1)) * 4, 256) + 2 * 256;
+  return fsf_layout_bytes<GpLayout>((n > 0 ? n : 1) * (ng > 0 ? ng : 1));
 }
 
 extern "C" int fsf_group_pairs(const float* score, int64_t n, int32_t ng, int64_t score_stride, const float* thresh, int32_t keep_one,
@@ -633,21 +643,16 @@ extern "C" int fsf_group_pairs(const float* score, int64_t n, int32_t ng, int64_
   if (capacity < n * ng) return FSF_ERR_CAPACITY;  // (the caller allocates the upper bound: the count is only known afterwards)
   *count_host = 0;
   if (n == 0) return FSF_OK;
-  if (!workspace || workspace_bytes < fsf_group_pairs_workspace_bytes(n, ng)) return FSF_ERR_WORKSPACE;
-  FsfArena ar(workspace, workspace_bytes);
-  uint32_t* any_mask = ar.take<uint32_t>(1);  // [any_mask | the scan's tile words]: one memset
-  uint32_t* tiles = ar.take<uint32_t>(scan_num_tiles(n * ng));
-  int64_t* total = ar.take<int64_t>(1);
-  if (!ar.ok()) return FSF_ERR_WORKSPACE;
-  FSF_HIP_TRY(hipMemsetAsync(any_mask, 0, (size_t)((char*)total - (char*)any_mask), stream));
+  FSF_CARVE(GpLayout, l, workspace, workspace_bytes, n * ng);
+  FSF_HIP_TRY(hipMemsetAsync(l.any_mask, 0, l.zero_bytes, stream));
   if (keep_one)
     hipLaunchKernelGGL(gp_any_kernel, dim3(fsf_stream_grid(n, 256)), dim3(256), 0, stream, score, n, (int)ng, score_stride, thresh, groups,
-                       any_mask);
-  const int rc = exclusive_scan_u32(GpIn{score, n, score_stride, thresh, any_mask, (int)keep_one, groups}, GpOut{n, g_ids, p_ids}, n * ng, tiles, nullptr,
-                                    total, stream, 1, true);
+                       l.any_mask);
+  const int rc = exclusive_scan_u32(GpIn{score, n, score_stride, thresh, l.any_mask, (int)keep_one, groups}, GpOut{n, g_ids, p_ids}, n * ng, l.tiles, nullptr,
+                                    l.total, stream, 1, true);
   if (rc != FSF_OK) return rc;
   int64_t total_h = 0;
-  FSF_READ_BACK(&total_h, total, sizeof(int64_t), stream);
+  FSF_READ_BACK(&total_h, l.total, sizeof(int64_t), stream);
   *count_host = total_h;
   return FSF_OK;
 }
