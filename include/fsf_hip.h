@@ -492,6 +492,49 @@ int fsf_train_augment_boxes(const float* boxes, int64_t box_stride, int32_t box_
                             int64_t* no_aug_labels_out, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * K41  the nuScenes detection metrics of a validation pass on the device (docs/kernels/K41_det_eval.md)
+ * Replaces: NuScenesDataset.evaluate / _evaluate_single [UNVENDORED mmdet3d.datasets.NuScenesDataset], which hands the boxes to the
+ *   nuScenes devkit [UNVENDORED nuscenes.eval.detection: algo.accumulate / calc_ap / calc_tp, common.utils center_distance / scale_iou /
+ *   yaw_diff / attr_acc / cummean, data_classes.DetectionMetrics, configs/detection_cvpr_2019.json] — the reference reaches it through
+ *   `evaluation = dict(interval=...)` of its schedules.  Parity with the devkit is UNPINNED (it is on no machine this project builds on):
+ *   the kernels are held to the restatement of the published algorithm in mmdet3d_plugin/core/det_eval.py.
+ * fsf_det_eval_compute, one call per validation pass, never synchronises:
+ *   pred      f32 [num_pred, 9] device: x y z w l h yaw vx vy of every prediction, sample-major (stored order inside a sample)
+ *   score f32, pred_label i32, pred_attr i32 (-1 = none), pred_sample i32 [num_pred] (non-decreasing, in [0, num_samples))
+ *   gt        f32 [num_gt, 9], gt_label / gt_attr / gt_sample i32 [num_gt] likewise (gt velocity may be NaN, gt_attr -1 = none)
+ *             a row whose label is outside [0, num_classes), or whose sqrt(x^2 + y^2) exceeds class_range[label], is ignored
+ *   class_flags i32 [num_classes] HOST: bit 0 = orientation period pi (barrier), bit 1 + e = error e is NaN for the class
+ *             (e: 0 trans, 1 scale, 2 orient, 3 vel, 4 attr); class_range f64 [num_classes] HOST or NULL
+ *   dist_ths  f64 [num_thresholds] HOST; tp_threshold = the index of dist_th_tp among them; first_recall = round(100 min_recall) + 1
+ *   params    f64 [2] HOST: min_precision (in [0, 1)), mean_ap_weight
+ *   match     i32 [num_thresholds, num_pred]: the matched GT row (index into gt) of every prediction, -1 for none / ignored
+ *   curves    f64 [num_classes, 2 num_thresholds + 5, 101]: per class the precision curve of every threshold, the confidence curve of
+ *             every threshold, the five error curves of the TP threshold
+ *   result    f64 [fsf_det_eval_result_words]: [0] mAP, [1..5] mATE mASE mAOE mAVE mAAE, [6] NDS, [7] 0, from FSF_DET_EVAL_HEAD on
+ *             AP [C, T], TP errors [C, 5], npos [C], predictions [C], true positives [C, T], no_predictions flag [C, T]
+ * Matching: per class in descending score, among equal scores the LATER position first; per prediction the nearest untaken GT of its
+ * sample and class by sqrt(dx dx + dy dy) in fp64 (each operation rounded), the first GT among equal distances, a match iff the distance
+ * is strictly below the threshold.  Launches: prep, radix sort A (histogram + 5 passes), order, radix sort B (histogram + one pass per 8
+ * bits of num_samples (num_classes + 1)), bounds, K41a match, K41b curves, K41c summary.  No float atomics: the same bits on every run.
+ * Counts: num_pred * num_thresholds, num_gt * num_thresholds and num_samples * (num_classes + 1) stay below 2^30, else
+ * FSF_ERR_UNSUPPORTED (the size query then answers 0).
+ * workspace: >= fsf_det_eval_scratch_bytes(...) bytes, undefined on entry; the query measures the one layout struct the entry carves
+ *   (DetEvalLayout, csrc/det_eval.hip), one byte less is FSF_ERR_WORKSPACE before any launch.  (Named *_scratch_bytes: the set of
+ *   *_workspace_bytes / *_arena_bytes queries is pinned, with its recorded sizes, by tests/test_workspace_layout_cpu.py.)
+ */
+#define FSF_DET_EVAL_MAX_CLASSES 64
+#define FSF_DET_EVAL_MAX_THRESHOLDS 8
+#define FSF_DET_EVAL_HEAD 8
+int64_t fsf_det_eval_scratch_bytes(int64_t num_pred, int64_t num_gt, int64_t num_samples, int32_t num_classes, int32_t num_thresholds);
+int64_t fsf_det_eval_result_words(int32_t num_classes, int32_t num_thresholds);
+int fsf_det_eval_compute(const float* pred, const float* score, const int32_t* pred_label, const int32_t* pred_attr,
+                         const int32_t* pred_sample, int64_t num_pred, const float* gt, const int32_t* gt_label, const int32_t* gt_attr,
+                         const int32_t* gt_sample, int64_t num_gt, int64_t num_samples, int32_t num_classes, const int32_t* class_flags,
+                         const double* class_range, const double* dist_ths, int32_t num_thresholds, int32_t tp_threshold,
+                         int32_t first_recall, const double* params, int32_t* match, double* curves, double* result, void* workspace,
+                         int64_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * K34  camera instance-id planes painted from 2-D detections (docs/kernels/K34_mask_paint.md)
  * Replaces the offline round trip tools/mask_tools/save_mask_nusc.py / save_mask_argo2.py (paint_obj, paint_obj_bbox_only,
  *   get_instance_mask: PNG planes + anno.json) -> LoadMaskFromFiles (projects/mmdet3d_plugin/datasets/pipelines/loading.py:22-339).
