@@ -2,6 +2,7 @@
 // fused K21 + first K22s layer).  See include/fsf_hip.h and docs/kernels/K21_K22_linear_family.md.
 #pragma once
 #include "common.h"
+#include "operand_formats.h"
 
 namespace fsf {
 
@@ -64,21 +65,6 @@ __device__ __forceinline__ float lna_row_sum(float v) {
   return v;
 }
 
-// exact three-way split of 8 floats into bf16 planes (two bf16 per dword, element 2j in the low half)
-__device__ __forceinline__ void lna_split8(const float (&v)[8], lna_u32x4& hi, lna_u32x4& mid, lna_u32x4& lo) {
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    const float a = v[2 * j], b = v[2 * j + 1];
-    const float ah = __uint_as_float(__float_as_uint(a) & 0xffff0000u), bh = __uint_as_float(__float_as_uint(b) & 0xffff0000u);
-    const float ar = __fsub_rn(a, ah), br = __fsub_rn(b, bh);
-    const float am = __uint_as_float(__float_as_uint(ar) & 0xffff0000u), bm = __uint_as_float(__float_as_uint(br) & 0xffff0000u);
-    const float al = __fsub_rn(ar, am), bl = __fsub_rn(br, bm);
-    hi[j] = __builtin_amdgcn_perm(__float_as_uint(bh), __float_as_uint(ah), 0x07060302u);
-    mid[j] = __builtin_amdgcn_perm(__float_as_uint(bm), __float_as_uint(am), 0x07060302u);
-    lo[j] = __builtin_amdgcn_perm(__float_as_uint(bl), __float_as_uint(al), 0x07060302u);
-  }
-}
-
 typedef float lna_f32x2 __attribute__((ext_vector_type(2)));
 
 __device__ __forceinline__ lna_f32x2 lna_pk_fma(lna_f32x2 a, lna_f32x2 b, lna_f32x2 c) { return __builtin_elementwise_fma(a, b, c); }
@@ -95,29 +81,8 @@ __device__ __forceinline__ lna_f32x2 lna_act2(lna_f32x2 y, int act) {
   return y;
 }
 
-// ---- K22h: both operands as f16 hi | lo planes --------------------------------------------------------------------------
-// power of two s with s * amax in [2^13, 2^14) and inv = 1 / s (exact; the scheme of K9c / K9d, csrc/spconv_planes.hip):
-// hi = rn_f16(x s), lo = rn_f16(x s - hi): |x s - hi - lo| <= max(2^-22 |x s|, 2^-25), no f16 range hazard for any finite input
-__device__ __forceinline__ void lna_pick_scale(float amax, float& s, float& inv) {
-  int e = (int)((__float_as_uint(amax) >> 23) & 0xffu) - 127;
-  e = amax > 0.0f ? (e < -113 ? -113 : e) : 13;
-  s = __uint_as_float((unsigned)(13 - e + 127) << 23);
-  inv = __uint_as_float((unsigned)(e - 13 + 127) << 23);
-}
-
-__device__ __forceinline__ void lna_split8_f16(const float (&v)[8], float s, lna_u32x4& hi, lna_u32x4& lo) {
-  lna_f16x8 h, l;
-#pragma unroll
-  for (int e = 0; e < 8; ++e) {
-    const float xs = __fmul_rn(v[e], s);
-    h[e] = (_Float16)xs;
-    l[e] = (_Float16)__fsub_rn(xs, (float)h[e]);
-  }
-  hi = __builtin_bit_cast(lna_u32x4, h);
-  lo = __builtin_bit_cast(lna_u32x4, l);
-}
-
-constexpr unsigned LNA_F16_TAG = 0x4B323266u;  // "K22f": word 3 of the f16 weight planes' 256-byte header
+// ---- K22f / K22h: f16 hi | lo planes (fmt_pick_scale, fmt_split_f16: the scheme of K9c / K9d) -----------------------------------
+constexpr unsigned LNA_F16_TAG = 0x4B323266u;  // "K22f": word FMT_HDR_TAG of the f16 weight planes' header
 
 // ---- K22s: segmented max of the activated tile, rows sorted by segment ------------------------------------------------
 // Per 16-row group a segmented max-scan along the rows (16 lanes of a DPP row per channel quad), then per run:
@@ -397,7 +362,7 @@ __device__ __forceinline__ void lna_xf_scale_split(const float (&xc)[RG][8], int
     const auto r32 = __builtin_amdgcn_permlane32_swap(mb, mb, false, false);
     mb = max(r32[0], r32[1]);
     float s_new, inv_new;
-    lna_pick_scale(__uint_as_float(mb), s_new, inv_new);
+    fmt_pick_scale(__uint_as_float(mb), s_new, inv_new);
     if (kc == 0) {
       if (mb == 0u || s_new > xs_cap) { s_new = xs_cap; inv_new = xs_cap_inv; }
       ratio[rg] = s_new * w_scale;
@@ -409,7 +374,7 @@ __device__ __forceinline__ void lna_xf_scale_split(const float (&xc)[RG][8], int
     }
     xs_cur[rg] = s_new;
     xinv[rg] = inv_new;
-    lna_split8_f16(xc[rg], s_new, xh[rg], xl[rg]);
+    fmt_split_f16(xc[rg], s_new, xh[rg], xl[rg]);
   }
   if (__builtin_amdgcn_ballot_w64(changed) != 0) {  // (wave-uniform: rare after the first chunk)
 #pragma unroll

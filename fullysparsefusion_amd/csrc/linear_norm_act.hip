@@ -41,7 +41,7 @@ __global__ void __launch_bounds__(256)
 #pragma unroll
     for (int e = 0; e < 8; ++e) v[e] = (lc < slice_w && col < c && k0 + e < k) ? w[(int64_t)col * k + k0 + e] : 0.0f;
     lna_u32x4 hi, mid, lo;
-    lna_split8(v, hi, mid, lo);
+    fmt_split_bf16(v, hi, mid, lo);
     uint4* dst = planes + (((int64_t)slice * nkc + kc) * T + t) * 3 * 64 + lane;
     dst[0] = make_uint4(hi[0], hi[1], hi[2], hi[3]);
     dst[64] = make_uint4(mid[0], mid[1], mid[2], mid[3]);
@@ -49,27 +49,17 @@ __global__ void __launch_bounds__(256)
   }
 }
 
-// max |w| over the layer -> hdr[2] (bit pattern; cleared by the caller), one atomic per workgroup
-__global__ void __launch_bounds__(256) lna_weight_absmax_kernel(const float* __restrict__ w, int64_t n, unsigned* __restrict__ hdr) {
-  __shared__ float wave_max[4];
-  float amax = 0.0f;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) amax = fmaxf(amax, fabsf(w[i]));
-  amax = fsf_wave_max(amax);
-  if ((threadIdx.x & 63) == 0) wave_max[threadIdx.x >> 6] = amax;
-  __syncthreads();
-  if (threadIdx.x == 0) atomicMax(hdr + 2, __float_as_uint(fmaxf(fmaxf(wave_max[0], wave_max[1]), fmaxf(wave_max[2], wave_max[3]))));
-}
-
-// weight [c, k] fp32 -> header (inverse scale, scale, max |w| bits) + fragment-ordered f16 hi | lo planes of W * s_w
+// weight [c, k] fp32 -> header (inverse scale, scale, max |w| bits: already there, fsf_weight_layer_absmax) + fragment-ordered f16
+// hi | lo planes of W * s_w
 __global__ void __launch_bounds__(256)
     lna_prepare_f16_kernel(const float* __restrict__ w, int k, int c, int T, int nkc, int nslice, int slice_w, float* __restrict__ hdr,
                            uint4* __restrict__ planes) {
   float s_w, inv_w;
-  lna_pick_scale(__uint_as_float(reinterpret_cast<const unsigned*>(hdr)[2]), s_w, inv_w);
+  fmt_pick_scale(__uint_as_float(reinterpret_cast<const unsigned*>(hdr)[FMT_HDR_AMAX_BITS]), s_w, inv_w);
   if (blockIdx.x == 0 && threadIdx.x == 0) {
-    hdr[0] = inv_w;
-    hdr[1] = s_w;
-    reinterpret_cast<unsigned*>(hdr)[3] = LNA_F16_TAG;  // the format's tag word: the f16-weight kernels refuse a buffer without it
+    hdr[FMT_HDR_INV_SCALE] = inv_w;
+    hdr[FMT_HDR_SCALE] = s_w;
+    reinterpret_cast<unsigned*>(hdr)[FMT_HDR_TAG] = LNA_F16_TAG;  // the format's tag word: the f16-weight kernels refuse a buffer without it
   }
   const int64_t total = (int64_t)nslice * nkc * T * 64;
   for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (int64_t)gridDim.x * blockDim.x) {
@@ -82,7 +72,7 @@ __global__ void __launch_bounds__(256)
 #pragma unroll
     for (int e = 0; e < 8; ++e) v[e] = (lc < slice_w && col < c && k0 + e < k) ? w[(int64_t)col * k + k0 + e] : 0.0f;
     lna_u32x4 hi, lo;
-    lna_split8_f16(v, s_w, hi, lo);
+    fmt_split_f16(v, s_w, hi, lo);
     uint4* dst = planes + (((int64_t)slice * nkc + kc) * T + t) * 2 * 64 + lane;
     dst[0] = make_uint4(hi[0], hi[1], hi[2], hi[3]);
     dst[64] = make_uint4(lo[0], lo[1], lo[2], lo[3]);
@@ -160,14 +150,14 @@ __global__ void __launch_bounds__(256)
       for (int e = 0; e < 8; ++e) amax = fmaxf(amax, fabsf(v[b][e]));
     amax = fsf_wave_max(amax);
     float s_row, inv_row;
-    lna_pick_scale(amax, s_row, inv_row);
+    fmt_pick_scale(amax, s_row, inv_row);
     if (lane == 0) inv_scales[row] = inv_row;
 #pragma unroll
     for (int b = 0; b < BL; ++b) {
       const int blk = lane + 64 * b;
       if (blk < nb) {
         lna_u32x4 hi, lo;
-        lna_split8_f16(v[b], s_row, hi, lo);
+        fmt_split_f16(v[b], s_row, hi, lo);
         uint4* dst = planes + (row * nb + blk) * 2;
         dst[0] = make_uint4(hi[0], hi[1], hi[2], hi[3]);
         dst[1] = make_uint4(lo[0], lo[1], lo[2], lo[3]);
@@ -217,8 +207,8 @@ __global__ void __launch_bounds__(LNA_NW * 64, SEG ? LNA_SEG_WPS : LNA_WPS) line
     blk_step = gridDim.x / nslice;
   }
   const int ch_base = a.slice_w * slice_id;
-  const uint4* planes = a.planes + (XM != 0 ? 16 : 0) + (int64_t)slice_id * nkc * CHUNK_U4;  // (f16 planes: behind the 256-byte header)
-  if (XM != 0 && reinterpret_cast<const unsigned*>(a.planes)[3] != LNA_F16_TAG)
+  const uint4* planes = a.planes + (XM != 0 ? FMT_HDR_U4 : 0) + (int64_t)slice_id * nkc * CHUNK_U4;  // (f16 planes: behind the 256-byte header)
+  if (XM != 0 && reinterpret_cast<const unsigned*>(a.planes)[FMT_HDR_TAG] != LNA_F16_TAG)
     __builtin_trap();  // a buffer that fsf_linear_prepare_weight_f16 did not write: the launch fails loudly instead of multiplying garbage
 
   // weight chunk kc -> LDS buffer by LDS-DMA: fragment order in HBM == fragment order in LDS, 1 KB per wave instruction
@@ -270,9 +260,9 @@ __global__ void __launch_bounds__(LNA_NW * 64, SEG ? LNA_SEG_WPS : LNA_WPS) line
   // it could not contribute next to an addend anyway); without one, any scale a finite row asks for
   float w_scale = 1.0f, xs_cap = 0x1p126f, xs_cap_inv = 0x1p-126f;
   if constexpr (XF) {
-    w_scale = reinterpret_cast<const float*>(a.planes)[1];
+    w_scale = reinterpret_cast<const float*>(a.planes)[FMT_HDR_SCALE];
     if (a.row_add) {
-      int e = (int)((__float_as_uint(reinterpret_cast<const float*>(a.planes)[0]) >> 23) & 0xffu) - 127 + 40;
+      int e = (int)((__float_as_uint(reinterpret_cast<const float*>(a.planes)[FMT_HDR_INV_SCALE]) >> 23) & 0xffu) - 127 + 40;
       e = e < -126 ? -126 : (e > 126 ? 126 : e);
       xs_cap = __uint_as_float((unsigned)(e + 127) << 23);
       xs_cap_inv = __uint_as_float((unsigned)(127 - e) << 23);
@@ -363,7 +353,7 @@ __global__ void __launch_bounds__(LNA_NW * 64, SEG ? LNA_SEG_WPS : LNA_WPS) line
       }
       if constexpr (XM == 0) {
 #pragma unroll
-        for (int rg = 0; rg < LNA_RG; ++rg) lna_split8(xc[rg], xh[rg], xm[rg], xl[rg]);
+        for (int rg = 0; rg < LNA_RG; ++rg) fmt_split_bf16(xc[rg], xh[rg], xm[rg], xl[rg]);
       }
       if constexpr (XF) {
         // K22f: the row's running power-of-two scale, the f16 hi | lo split and, where the scale fell, the accumulators' rescale
@@ -416,7 +406,7 @@ __global__ void __launch_bounds__(LNA_NW * 64, SEG ? LNA_SEG_WPS : LNA_WPS) line
       }
     }
     if constexpr (XM != 0) {  // back to the unscaled product: both scales are powers of two (exact)
-      const float w_inv = *reinterpret_cast<const float*>(a.planes);
+      const float w_inv = reinterpret_cast<const float*>(a.planes)[FMT_HDR_INV_SCALE];
 #pragma unroll
       for (int rg = 0; rg < LNA_RG; ++rg) {
         const float sc = xinv[rg] * w_inv;
@@ -655,7 +645,7 @@ extern "C" int fsf_linear_f16w_norm_act_segmax(const float* x, int64_t n, int32_
 extern "C" int64_t fsf_linear_prepared_weight_f16_bytes(int32_t k, int32_t c, int32_t slice_c) {
   if (k < 1 || c < 1 || slice_c < 1 || slice_c > 128) return 0;
   const int64_t nkc = (k + LNA_KC - 1) / LNA_KC, nslice = (c + slice_c - 1) / slice_c;
-  return 256 + nslice * nkc * lna_tiles(slice_c) * 2 * 64 * 16;
+  return FMT_HDR_BYTES + nslice * nkc * lna_tiles(slice_c) * 2 * 64 * 16;
 }
 
 extern "C" int fsf_linear_prepare_weight_f16(const float* weight, int32_t k, int32_t c, int32_t slice_c, void* planes, void* stream_) {
@@ -663,14 +653,11 @@ extern "C" int fsf_linear_prepare_weight_f16(const float* weight, int32_t k, int
   if (!weight || !planes || k < 1 || c < 1 || slice_c < 1 || slice_c > 128) return FSF_ERR_INVALID_ARG;
   if (((uintptr_t)planes % 16) != 0) return FSF_ERR_UNSUPPORTED;
   const int T = lna_tiles(slice_c), nkc = (k + LNA_KC - 1) / LNA_KC, nslice = (c + slice_c - 1) / slice_c;
-  FSF_HIP_TRY(hipMemsetAsync(planes, 0, 256, stream));
-  const int64_t nw = (int64_t)c * k;
-  // (at most 256 workgroups: each ends in ONE atomic on the same word — 2 048 of them took 25 us for a 1 M-element weight)
-  hipLaunchKernelGGL(lna_weight_absmax_kernel, dim3(std::min(fsf_stream_grid(nw, 256), 256)), dim3(256), 0, stream, weight, nw, (unsigned*)planes);
-  FSF_LAUNCH_CHECK();
+  const int rc = fsf_weight_layer_absmax(weight, (int64_t)c * k, planes, stream);
+  if (rc != FSF_OK) return rc;
   const int64_t total = (int64_t)nslice * nkc * T * 64;
   hipLaunchKernelGGL(lna_prepare_f16_kernel, dim3(fsf_stream_grid(total, 256)), dim3(256), 0, stream, weight, (int)k, (int)c, T, nkc,
-                     nslice, (int)slice_c, (float*)planes, (uint4*)planes + 16);
+                     nslice, (int)slice_c, (float*)planes, (uint4*)planes + FMT_HDR_U4);
   FSF_LAUNCH_CHECK();
   return FSF_OK;
 }

@@ -120,12 +120,12 @@ __global__ void __launch_bounds__(SL_NW * 64, 1) sir_linear_kernel(SirInputArgs 
   uint4* wbuf = reinterpret_cast<uint4*>(sl_smem + si_smem_bytes<NT3, SL_NW>());
   float* vec = reinterpret_cast<float*>(wbuf + 2 * SL_CHUNK_U4);
   LnaSegSmem* segsm = reinterpret_cast<LnaSegSmem*>(vec + 384);
-  if (reinterpret_cast<const unsigned*>(a.planes)[3] != LNA_F16_TAG)
+  if (reinterpret_cast<const unsigned*>(a.planes)[FMT_HDR_TAG] != LNA_F16_TAG)
     __builtin_trap();  // a buffer that fsf_linear_prepare_weight_f16 did not write: the launch fails loudly instead of multiplying garbage
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  SlDriver<NT3, ACT> d{a, wbuf, vec, segsm, a.planes + 16, lane, wave, lane & 15, lane >> 4, (a.k + LNA_KC - 1) / LNA_KC, a.k,
+  SlDriver<NT3, ACT> d{a, wbuf, vec, segsm, a.planes + FMT_HDR_U4, lane, wave, lane & 15, lane >> 4, (a.k + LNA_KC - 1) / LNA_KC, a.k,
                        (int64_t)blockIdx.x, (int64_t)gridDim.x, (a.n + SL_ROWS - 1) / SL_ROWS, (a.n + 15) / 16, 0,
-                       reinterpret_cast<const float*>(a.planes)[1], reinterpret_cast<const float*>(a.planes)[0]};
+                       reinterpret_cast<const float*>(a.planes)[FMT_HDR_SCALE], reinterpret_cast<const float*>(a.planes)[FMT_HDR_INV_SCALE]};
   lna_stage_vectors(a, 0, vec);
   d.stage_w(0, 0);
   si_run<NT3, ACT, SL_NW>(si, si_smem, d);

@@ -20,6 +20,7 @@
 #include <stdlib.h>
 
 #include "common.h"
+#include "operand_formats.h"
 
 namespace fsf {
 
@@ -241,21 +242,6 @@ constexpr int BWS_PLANE = 128 * BWS_ROW;          // one plane of one operand
 constexpr int BWS_OPER = 3 * BWS_PLANE;           // hi | mid | lo
 constexpr int BWS_SMEM = 2 * BWS_OPER;            // A | B: 48 KB
 
-// 4 values (the same channel of 4 consecutive pairs) -> three 8-byte groups of bf16 (element e in the low / high half of dword e / 2)
-__device__ __forceinline__ void bws_split4(const float (&v)[4], bw_u32x2& hi, bw_u32x2& mid, bw_u32x2& lo) {
-#pragma unroll
-  for (int j = 0; j < 2; ++j) {
-    const float a = v[2 * j], b = v[2 * j + 1];
-    const float ah = __uint_as_float(__float_as_uint(a) & 0xffff0000u), bh = __uint_as_float(__float_as_uint(b) & 0xffff0000u);
-    const float ar = __fsub_rn(a, ah), br = __fsub_rn(b, bh);
-    const float am = __uint_as_float(__float_as_uint(ar) & 0xffff0000u), bm = __uint_as_float(__float_as_uint(br) & 0xffff0000u);
-    const float al = __fsub_rn(ar, am), bl = __fsub_rn(br, bm);
-    hi[j] = __builtin_amdgcn_perm(__float_as_uint(bh), __float_as_uint(ah), 0x07060302u);
-    mid[j] = __builtin_amdgcn_perm(__float_as_uint(bm), __float_as_uint(am), 0x07060302u);
-    lo[j] = __builtin_amdgcn_perm(__float_as_uint(bl), __float_as_uint(al), 0x07060302u);
-  }
-}
-
 __global__ void __launch_bounds__(256, 2) spconv_bwd_weight_split_kernel(SpconvBwdArgs a) {
   extern __shared__ __attribute__((aligned(16))) char bws_smem[];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -309,8 +295,8 @@ __global__ void __launch_bounds__(256, 2) spconv_bwd_weight_split_kernel(SpconvB
         float v[4];
 #pragma unroll
         for (int r = 0; r < 4; ++r) v[r] = p0 + r < p_end ? (oper == 0 ? xa[r][c] : xb[r][c]) : 0.0f;
-        bw_u32x2 hi, mid, lo;
-        bws_split4(v, hi, mid, lo);
+        bw_u32x2 hi, mid, lo;  // 4 values (the same channel of 4 consecutive pairs) -> three 8-byte groups of bf16
+        fmt_split_bf16(v, hi, mid, lo);
         *reinterpret_cast<bw_u32x2*>(base) = hi;
         *reinterpret_cast<bw_u32x2*>(base + BWS_PLANE) = mid;
         *reinterpret_cast<bw_u32x2*>(base + 2 * BWS_PLANE) = lo;

@@ -30,6 +30,7 @@
 #include <type_traits>
 
 #include "common.h"
+#include "operand_formats.h"
 
 namespace fsf {
 
@@ -41,31 +42,11 @@ typedef unsigned sp_u32x2 __attribute__((ext_vector_type(2)));
 
 constexpr int SP_NSLOT = 2;      // gathered-row ring in LDS: step s is multiplied from slot s % 2 while X(s + 1) is written to the other
 constexpr int SP_KVOL_MAX = 27;
-constexpr int SP_HDR_BYTES = 256;  // weight-plane header: [0] inverse weight scale, [1] weight scale, [2] max |w| bits
 
 // Which 8-wide k group of a 32-cin chunk lane group q = lane / 16 multiplies: sigma = (0, 3, 1, 2).  The MFMA sums over k, so any
 // assignment works as long as the weight fragments (sp_weight_planes_kernel) and the X fragments agree; THIS one makes K9d's
 // row-major LDS tile (written by line-coalesced gathers, swizzled per row) readable by ds_read_b128 without bank conflicts.
 __device__ __forceinline__ int sp_kgroup(int q) { return (0x9C >> (2 * q)) & 3; }
-// power of two s with s * amax in [2^13, 2^14); inv = 1 / s (both exact)
-__device__ __forceinline__ void sp_pick_scale(float amax, float& s, float& inv) {
-  int e = (int)((__float_as_uint(amax) >> 23) & 0xffu) - 127;
-  e = amax > 0.0f ? (e < -113 ? -113 : e) : 13;  // (s and inv stay normal fp32 numbers for every finite amax)
-  s = __uint_as_float((unsigned)(13 - e + 127) << 23);
-  inv = __uint_as_float((unsigned)(e - 13 + 127) << 23);
-}
-
-__device__ __forceinline__ void sp_split4(const float (&v)[4], float s, sp_u32x2& hi, sp_u32x2& lo) {
-  sp_f16x4 h, l;
-#pragma unroll
-  for (int e = 0; e < 4; ++e) {
-    const float xs = __fmul_rn(v[e], s);
-    h[e] = (_Float16)xs;
-    l[e] = (_Float16)__fsub_rn(xs, (float)h[e]);
-  }
-  hi = __builtin_bit_cast(sp_u32x2, h);
-  lo = __builtin_bit_cast(sp_u32x2, l);
-}
 
 // ---------------------------------------------------------------------------------------------------------------------
 // fp32 rows -> planes.  planes: [m + 1][c / 8][2][8] f16 (row m = zeros, the neighbour of a missing pair);
@@ -97,12 +78,12 @@ __global__ void __launch_bounds__(256)
 #pragma unroll
     for (int o = 8; o > 0; o >>= 1) amax = fmaxf(amax, __shfl_xor(amax, o, 16));
     float s, inv;
-    sp_pick_scale(amax, s, inv);
+    fmt_pick_scale(amax, s, inv);
     if (active) {
       sp_u32x2 h0, l0, h1, l1;
       const float a4[4] = {v[0], v[1], v[2], v[3]}, b4[4] = {v[4], v[5], v[6], v[7]};
-      sp_split4(a4, s, h0, l0);
-      sp_split4(b4, s, h1, l1);
+      fmt_split_f16(a4, s, h0, l0);
+      fmt_split_f16(b4, s, h1, l1);
       uint4* dst = planes + (row * (c / 8) + (c0 >> 3)) * 2;
       dst[0] = make_uint4(h0[0], h0[1], h1[0], h1[1]);
       dst[1] = make_uint4(l0[0], l0[1], l1[0], l1[1]);
@@ -151,12 +132,12 @@ __global__ void __launch_bounds__(256)
 #pragma unroll
     for (int o = 8; o > 0; o >>= 1) amax = fmaxf(amax, __shfl_xor(amax, o, 16));
     float s, inv;
-    sp_pick_scale(amax, s, inv);
+    fmt_pick_scale(amax, s, inv);
     if (active) {
       sp_u32x2 h0, l0, h1, l1;
       const float a4[4] = {v[0], v[1], v[2], v[3]}, b4[4] = {v[4], v[5], v[6], v[7]};
-      sp_split4(a4, s, h0, l0);
-      sp_split4(b4, s, h1, l1);
+      fmt_split_f16(a4, s, h0, l0);
+      fmt_split_f16(b4, s, h1, l1);
       uint4* dst = planes + (row * (c / 8) + (c0 >> 3)) * 2;
       dst[0] = make_uint4(h0[0], h0[1], h1[0], h1[1]);
       dst[1] = make_uint4(l0[0], l0[1], l1[0], l1[1]);
@@ -167,38 +148,15 @@ __global__ void __launch_bounds__(256)
 
 // ---------------------------------------------------------------------------------------------------------------------
 // weights [kvol][cin][cout] fp32 (spconv v1 layout) -> per-wave A-fragment planes of W_k^T, one power-of-two scale per layer
-__global__ void __launch_bounds__(256) sp_weight_absmax_kernel(const float* __restrict__ w, int64_t n, unsigned* __restrict__ hdr) {
-  __shared__ float wave_max[4];
-  float amax = 0.0f;
-  // 16-byte loads over the aligned body; the (at most 3 + 3) scalars in front of / behind it go to workgroup 0
-  const int64_t head = std::min<int64_t>(n, (int64_t)(((16 - (reinterpret_cast<uintptr_t>(w) & 15)) & 15) >> 2));
-  const int64_t n4 = (n - head) >> 2;
-  const float4* w4 = reinterpret_cast<const float4*>(w + head);
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (int64_t)gridDim.x * blockDim.x) {
-    const float4 v = w4[i];
-    amax = fmaxf(fmaxf(amax, fabsf(v.x)), fmaxf(fabsf(v.y), fmaxf(fabsf(v.z), fabsf(v.w))));
-  }
-  if (blockIdx.x == 0) {
-    if ((int64_t)threadIdx.x < head) amax = fmaxf(amax, fabsf(w[threadIdx.x]));
-    const int64_t tail0 = head + (n4 << 2);
-    if (tail0 + threadIdx.x < n && threadIdx.x < 4) amax = fmaxf(amax, fabsf(w[tail0 + threadIdx.x]));
-  }
-  amax = fsf_wave_max(amax);
-  if ((threadIdx.x & 63) == 0) wave_max[threadIdx.x >> 6] = amax;
-  __syncthreads();
-  // one atomic per workgroup (per-wave atomics on the one address were the whole cost of this kernel: 84 us for 1.8 MB)
-  if (threadIdx.x == 0)
-    atomicMax(hdr + 2, __float_as_uint(fmaxf(fmaxf(wave_max[0], wave_max[1]), fmaxf(wave_max[2], wave_max[3]))));  // |x| bit patterns order like the values
-}
-
+// (max |w| is in the header already: fsf_weight_layer_absmax)
 __global__ void __launch_bounds__(256)
     sp_weight_planes_kernel(const float* __restrict__ w, int kvol, int cin, int cout, int tpw, int nslice, float* __restrict__ hdr,
                             uint4* __restrict__ frag) {
   float s, inv;
-  sp_pick_scale(__uint_as_float(reinterpret_cast<const unsigned*>(hdr)[2]), s, inv);
+  fmt_pick_scale(__uint_as_float(reinterpret_cast<const unsigned*>(hdr)[FMT_HDR_AMAX_BITS]), s, inv);
   if (blockIdx.x == 0 && threadIdx.x == 0) {
-    hdr[0] = inv;
-    hdr[1] = s;
+    hdr[FMT_HDR_INV_SCALE] = inv;
+    hdr[FMT_HDR_SCALE] = s;
   }
   const int nchunks = cin / 32;
   const int64_t total = (int64_t)nslice * kvol * nchunks * 4 * tpw * 64;
@@ -217,8 +175,8 @@ __global__ void __launch_bounds__(256)
     for (int e = 0; e < 8; ++e) v[e] = col < cout ? w[((int64_t)k * cin + c0 + e) * cout + col] : 0.0f;
     sp_u32x2 h0, l0, h1, l1;
     const float a4[4] = {v[0], v[1], v[2], v[3]}, b4[4] = {v[4], v[5], v[6], v[7]};
-    sp_split4(a4, s, h0, l0);
-    sp_split4(b4, s, h1, l1);
+    fmt_split_f16(a4, s, h0, l0);
+    fmt_split_f16(b4, s, h1, l1);
     uint4* dst = frag + ((idx >> 6) * 2) * 64 + lane;
     dst[0] = make_uint4(h0[0], h0[1], h1[0], h1[1]);
     dst[64] = make_uint4(l0[0], l0[1], l1[0], l1[1]);
@@ -298,7 +256,7 @@ __device__ __forceinline__ void sp_epilogue(const SpArgs& a, sp_f32x4 (&acc)[RG]
       const int rl = 16 * g + j;
       const float m = fmaxf(fmaxf(rowmax[rl], rowmax[R + rl]), fmaxf(rowmax[2 * R + rl], rowmax[3 * R + rl]));
       float sc, inv_s;
-      sp_pick_scale(m, sc, inv_s);
+      fmt_pick_scale(m, sc, inv_s);
       if (row < a.m_out) {
 #pragma unroll
         for (int t = 0; t < TPW; ++t) {
@@ -306,7 +264,7 @@ __device__ __forceinline__ void sp_epilogue(const SpArgs& a, sp_f32x4 (&acc)[RG]
           if (ch < a.cout) {
             const float v4[4] = {acc[g][t][0], acc[g][t][1], acc[g][t][2], acc[g][t][3]};
             sp_u32x2 hi, lo;
-            sp_split4(v4, sc, hi, lo);
+            fmt_split_f16(v4, sc, hi, lo);
             char* dst = reinterpret_cast<char*>(a.out_planes + (row * blocks_per_row + (ch >> 3)) * 2) + (q & 1) * 8;
             *reinterpret_cast<sp_u32x2*>(dst) = hi;
             *reinterpret_cast<sp_u32x2*>(dst + 16) = lo;
@@ -413,7 +371,7 @@ __global__ void __launch_bounds__(256, RG == 8 ? 1 : SP_RG4_WPS) spconv_fwd_plan
   const int nkc0 = FIX ? NKC : a.c[0] / 32, nkc1 = FIX ? (nsrc == 2 ? NKC : 0) : a.c[1] / 32;
   const int nchunks = nkc0 + nkc1;  // 32-cin chunks of the concatenated input (the weight fragments are laid out over them)
   const int nsteps = nk * nsrc;
-  const float w_inv = a.w_hdr[0];
+  const float w_inv = a.w_hdr[FMT_HDR_INV_SCALE];
   const uint32_t rowbytes0 = (uint32_t)a.c[0] * 4u, rowbytes1 = (uint32_t)a.c[1] * 4u;
 
   auto entry = [&](int kidx, int src) -> SpStep {
@@ -710,7 +668,7 @@ __global__ void __launch_bounds__(256, SP_PIPE_WPS) spconv_fwd_pipe_kernel(SpArg
   const int nsrc = a.c[1] > 0 ? 2 : 1;
   const int nchunks = NKC * nsrc;
   const int nsteps = nk * nsrc;
-  const float w_inv = a.w_hdr[0];
+  const float w_inv = a.w_hdr[FMT_HDR_INV_SCALE];
   const uint32_t rowbytes = (uint32_t)NKC * 128u;  // both sources are NKC * 32 channels wide
 
   auto entry = [&](int kidx, int src) -> SpStep {
@@ -963,21 +921,19 @@ extern "C" int fsf_channel_pair_sum_add2_planes(const float* feat_a, int32_t ca,
 
 extern "C" int64_t fsf_spconv_planes_weight_bytes(int32_t kvol, int32_t cin, int32_t cout) {
   if (kvol < 1 || cin < 32 || (cin % 32) != 0 || cout < 1) return 0;
-  return SP_HDR_BYTES + (int64_t)sp_nslice(cout) * kvol * (cin / 32) * 4 * sp_tpw(cout) * 2 * 64 * 16;
+  return FMT_HDR_BYTES + (int64_t)sp_nslice(cout) * kvol * (cin / 32) * 4 * sp_tpw(cout) * 2 * 64 * 16;
 }
 
 extern "C" int fsf_spconv_prepare_weight_planes(const float* weight, int32_t kvol, int32_t cin, int32_t cout, void* planes,
                                                 void* stream_) {
   hipStream_t stream = (hipStream_t)stream_;
   if (!weight || !planes || kvol < 1 || cin < 32 || (cin % 32) != 0 || cout < 1) return FSF_ERR_INVALID_ARG;
-  FSF_HIP_TRY(hipMemsetAsync(planes, 0, SP_HDR_BYTES, stream));
-  const int64_t n = (int64_t)kvol * cin * cout;
-  hipLaunchKernelGGL(sp_weight_absmax_kernel, dim3((unsigned)std::min<int64_t>(256, (n / 4 + 255) / 256 + 1)), dim3(256), 0, stream, weight, n,
-                     (unsigned*)planes);
+  const int rc = fsf_weight_layer_absmax(weight, (int64_t)kvol * cin * cout, planes, stream);
+  if (rc != FSF_OK) return rc;
   const int tpw = sp_tpw(cout), nslice = sp_nslice(cout);
   const int64_t total = (int64_t)nslice * kvol * (cin / 32) * 4 * tpw * 64;
   hipLaunchKernelGGL(sp_weight_planes_kernel, dim3(fsf_stream_grid(total, 256)), dim3(256), 0, stream, weight, (int)kvol, (int)cin,
-                     (int)cout, tpw, nslice, (float*)planes, (uint4*)((char*)planes + SP_HDR_BYTES));
+                     (int)cout, tpw, nslice, (float*)planes, (uint4*)((char*)planes + FMT_HDR_BYTES));
   FSF_LAUNCH_CHECK();
   return FSF_OK;
 }
@@ -1014,7 +970,7 @@ extern "C" int fsf_spconv_forward_planes(const void* xa, const float* sa, int32_
   a.x[0] = (const char*)xa; a.x[1] = (const char*)xb;
   a.sx[0] = sa; a.sx[1] = sb;
   a.c[0] = ca; a.c[1] = cb;
-  a.w = (const sp_u32x4*)((const char*)wplanes + SP_HDR_BYTES);
+  a.w = (const sp_u32x4*)((const char*)wplanes + FMT_HDR_BYTES);
   a.w_hdr = (const float*)wplanes;
   a.nbr = nbr; a.m_in = m_in; a.m_out = m_out;
   a.kvol = kvol; a.cin = ca + cb; a.cout = cout; a.relu = relu;

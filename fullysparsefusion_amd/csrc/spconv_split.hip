@@ -21,6 +21,7 @@
 #include <algorithm>
 
 #include "common.h"
+#include "operand_formats.h"
 
 namespace fsf {
 
@@ -60,20 +61,6 @@ struct ScsArgs {
   const float* x_inv_scale;
 };
 
-__device__ __forceinline__ void scs_split8(const float (&v)[8], scs_u32x4& hi, scs_u32x4& mid, scs_u32x4& lo) {
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    const float a = v[2 * j], b = v[2 * j + 1];
-    const float ah = __uint_as_float(__float_as_uint(a) & 0xffff0000u), bh = __uint_as_float(__float_as_uint(b) & 0xffff0000u);
-    const float ar = __fsub_rn(a, ah), br = __fsub_rn(b, bh);
-    const float am = __uint_as_float(__float_as_uint(ar) & 0xffff0000u), bm = __uint_as_float(__float_as_uint(br) & 0xffff0000u);
-    const float al = __fsub_rn(ar, am), bl = __fsub_rn(br, bm);
-    hi[j] = __builtin_amdgcn_perm(__float_as_uint(bh), __float_as_uint(ah), 0x07060302u);
-    mid[j] = __builtin_amdgcn_perm(__float_as_uint(bm), __float_as_uint(am), 0x07060302u);
-    lo[j] = __builtin_amdgcn_perm(__float_as_uint(bl), __float_as_uint(al), 0x07060302u);
-  }
-}
-
 // weight [kvol][cin][cout] fp32 (the spconv v1 layout) -> fragment-ordered bf16 planes of W_k^T
 __global__ void __launch_bounds__(256)
     scs_prepare_kernel(const float* __restrict__ w, int kvol, int cin, int cout, int T, int nkc, int nslice, uint4* planes) {
@@ -90,7 +77,7 @@ __global__ void __launch_bounds__(256)
 #pragma unroll
     for (int e = 0; e < 8; ++e) v[e] = (col < cout && c0 + e < cin) ? w[((int64_t)k * cin + c0 + e) * cout + col] : 0.0f;
     scs_u32x4 hi, mid, lo;
-    scs_split8(v, hi, mid, lo);
+    fmt_split_bf16(v, hi, mid, lo);
     uint4* dst = planes + ((((int64_t)slice * kvol + k) * nkc + kc) * T + t) * 3 * 64 + lane;
     dst[0] = make_uint4(hi[0], hi[1], hi[2], hi[3]);
     dst[64] = make_uint4(mid[0], mid[1], mid[2], mid[3]);
@@ -99,29 +86,13 @@ __global__ void __launch_bounds__(256)
 }
 
 // ---- K9b-XP weights: one power-of-two scale per layer (s * max |w| in [2^13, 2^14)), hi = rn_f16(w s), lo = rn_f16(w s - hi)
-__device__ __forceinline__ void scs_pick_scale(float amax, float& s, float& inv) {
-  int e = (int)((__float_as_uint(amax) >> 23) & 0xffu) - 127;
-  e = amax > 0.0f ? (e < -113 ? -113 : e) : 13;
-  s = __uint_as_float((unsigned)(13 - e + 127) << 23);
-  inv = __uint_as_float((unsigned)(e - 13 + 127) << 23);
-}
-
-__global__ void __launch_bounds__(256) scs_weight_absmax_kernel(const float* __restrict__ w, int64_t n, unsigned* __restrict__ hdr) {
-  __shared__ float wave_max[4];
-  float amax = 0.0f;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) amax = fmaxf(amax, fabsf(w[i]));
-  amax = fsf_wave_max(amax);
-  if ((threadIdx.x & 63) == 0) wave_max[threadIdx.x >> 6] = amax;
-  __syncthreads();
-  if (threadIdx.x == 0) atomicMax(hdr + 2, __float_as_uint(fmaxf(fmaxf(wave_max[0], wave_max[1]), fmaxf(wave_max[2], wave_max[3]))));
-}
-
+// (max |w| is in the header already: fsf_weight_layer_absmax)
 __global__ void __launch_bounds__(256)
     scs_prepare_f16_kernel(const float* __restrict__ w, int kvol, int cin, int cout, int T, int nkc, int nslice, float* __restrict__ hdr,
                            uint4* __restrict__ planes) {
   float s_w, inv_w;
-  scs_pick_scale(__uint_as_float(reinterpret_cast<const unsigned*>(hdr)[2]), s_w, inv_w);
-  if (blockIdx.x == 0 && threadIdx.x == 0) { hdr[0] = inv_w; hdr[1] = s_w; }
+  fmt_pick_scale(__uint_as_float(reinterpret_cast<const unsigned*>(hdr)[FMT_HDR_AMAX_BITS]), s_w, inv_w);
+  if (blockIdx.x == 0 && threadIdx.x == 0) { hdr[FMT_HDR_INV_SCALE] = inv_w; hdr[FMT_HDR_SCALE] = s_w; }
   const int64_t total = (int64_t)nslice * kvol * nkc * T * 64;
   for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (int64_t)gridDim.x * blockDim.x) {
     const int lane = (int)(idx & 63);
@@ -131,15 +102,11 @@ __global__ void __launch_bounds__(256)
     const int k = (int)(r % kvol);
     const int slice = (int)(r / kvol);
     const int col = 128 * slice + 16 * t + (lane & 15), c0 = kc * SCS_KC + 8 * (lane >> 4);
-    scs_f16x8 h, l;
+    float v[8];
 #pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      const float v = (col < cout && c0 + e < cin) ? w[((int64_t)k * cin + c0 + e) * cout + col] : 0.0f;
-      const float xs = __fmul_rn(v, s_w);
-      h[e] = (_Float16)xs;
-      l[e] = (_Float16)__fsub_rn(xs, (float)h[e]);
-    }
-    const scs_u32x4 hi = __builtin_bit_cast(scs_u32x4, h), lo = __builtin_bit_cast(scs_u32x4, l);
+    for (int e = 0; e < 8; ++e) v[e] = (col < cout && c0 + e < cin) ? w[((int64_t)k * cin + c0 + e) * cout + col] : 0.0f;
+    scs_u32x4 hi, lo;
+    fmt_split_f16(v, s_w, hi, lo);
     uint4* dst = planes + ((((int64_t)slice * kvol + k) * nkc + kc) * T + t) * 2 * 64 + lane;
     dst[0] = make_uint4(hi[0], hi[1], hi[2], hi[3]);
     dst[64] = make_uint4(lo[0], lo[1], lo[2], lo[3]);
@@ -174,7 +141,7 @@ __global__ void __launch_bounds__(SCS_NW * 64, SCS_WPS) spconv_fwd_split_kernel(
   const int ci_begin = (int)((int64_t)nchunks * bz / a.ksplit), ci_end = (int)((int64_t)nchunks * (bz + 1) / a.ksplit);
   const int64_t nblk = (a.m_out + SCS_ROWS - 1) / SCS_ROWS;
   const int ch_base = 128 * by;
-  const uint4* planes = a.planes + (XP ? 16 : 0) + (int64_t)by * nchunks * CHUNK_U4;  // (XP: behind the 256-byte header)
+  const uint4* planes = a.planes + (XP ? FMT_HDR_U4 : 0) + (int64_t)by * nchunks * CHUNK_U4;  // (XP: behind the 256-byte header)
   const int last_quad = a.cin - 4;
   // The epilogue's per-channel vectors go through LDS, and its residual row is loaded before the first store: as plain
   // global loads inside the tile loop each one sat behind the previous tile's store (the pointers may alias) — ~48
@@ -297,7 +264,7 @@ __global__ void __launch_bounds__(SCS_NW * 64, SCS_WPS) spconv_fwd_split_kernel(
           for (int e = 0; e < 8; ++e)
             if (kc * SCS_KC + 8 * grp + e >= a.cin) xc[rg][e] = 0.0f;
         }
-        scs_split8(xc[rg], xh[rg], xm[rg], xl[rg]);
+        fmt_split_bf16(xc[rg], xh[rg], xm[rg], xl[rg]);
         any_live |= live;
       }
       const bool wave_live = __ballot(any_live) != 0ull;  // does any of this wave's 32 rows have a neighbour at offset k?
@@ -381,7 +348,7 @@ __global__ void __launch_bounds__(SCS_NW * 64, SCS_WPS) spconv_fwd_split_kernel(
       }
     }
     if constexpr (XP) {  // back from the last rows' unit (and the weights') to the plain product
-      const float w_inv = *reinterpret_cast<const float*>(a.planes);
+      const float w_inv = reinterpret_cast<const float*>(a.planes)[FMT_HDR_INV_SCALE];
 #pragma unroll
       for (int rg = 0; rg < SCS_RG; ++rg) {
         const float sc = inv_cur[rg] * w_inv;
@@ -559,7 +526,7 @@ extern "C" int fsf_spconv_forward_split(const float* feat, int64_t m_in, int32_t
 extern "C" int64_t fsf_spconv_split_weight_f16_bytes(int32_t kvol, int32_t cin, int32_t cout) {
   if (kvol < 1 || cin < 1 || cout < 1) return 0;
   const int64_t nkc = (cin + SCS_KC - 1) / SCS_KC;
-  return 256 + (int64_t)scs_slices(cout) * kvol * nkc * scs_tiles(cout) * 2 * 64 * 16;
+  return FMT_HDR_BYTES + (int64_t)scs_slices(cout) * kvol * nkc * scs_tiles(cout) * 2 * 64 * 16;
 }
 
 extern "C" int fsf_spconv_prepare_weight_split_f16(const float* weight, int32_t kvol, int32_t cin, int32_t cout, void* planes,
@@ -568,14 +535,11 @@ extern "C" int fsf_spconv_prepare_weight_split_f16(const float* weight, int32_t 
   if (!weight || !planes || kvol < 1 || cin < 1 || cout < 1) return FSF_ERR_INVALID_ARG;
   if (((uintptr_t)planes % 16) != 0) return FSF_ERR_UNSUPPORTED;
   const int T = scs_tiles(cout), nkc = (cin + SCS_KC - 1) / SCS_KC, nslice = scs_slices(cout);
-  FSF_HIP_TRY(hipMemsetAsync(planes, 0, 256, stream));
-  const int64_t nw = (int64_t)kvol * cin * cout;
-  // (at most 256 workgroups: each ends in ONE atomic on the same word — 2 048 of them took 25 us for a 1 M-element weight)
-  hipLaunchKernelGGL(scs_weight_absmax_kernel, dim3(std::min(fsf_stream_grid(nw, 256), 256)), dim3(256), 0, stream, weight, nw, (unsigned*)planes);
-  FSF_LAUNCH_CHECK();
+  const int rc = fsf_weight_layer_absmax(weight, (int64_t)kvol * cin * cout, planes, stream);
+  if (rc != FSF_OK) return rc;
   const int64_t total = (int64_t)nslice * kvol * nkc * T * 64;
   hipLaunchKernelGGL(scs_prepare_f16_kernel, dim3(fsf_stream_grid(total, 256)), dim3(256), 0, stream, weight, (int)kvol, (int)cin,
-                     (int)cout, T, nkc, nslice, (float*)planes, (uint4*)planes + 16);
+                     (int)cout, T, nkc, nslice, (float*)planes, (uint4*)planes + FMT_HDR_U4);
   FSF_LAUNCH_CHECK();
   return FSF_OK;
 }

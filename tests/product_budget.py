@@ -32,7 +32,8 @@ LINEAR_N = (96, 129)        # six 16-row groups; a one-row tail after a 128-row 
 G_F16 = 3 * 2.0 ** -22
 U32 = 2.0 ** -23
 EPS_F16 = 2.0 ** -25        # absolute floor of hi + lo in the scaled unit (half the spacing of f16 subnormals)
-TOP_EXP = 13                # s * amax in [2^13, 2^14): sp_pick_scale / scs_pick_scale / lna_pick_scale
+TOP_EXP = 13                # s * amax in [2^13, 2^14): fmt_pick_scale (csrc/operand_formats.h)
+MIN_AMAX_EXP = -113         # ... with amax's exponent clamped from below: s <= 2^126, so that s and 1 / s stay normal fp32 numbers
 LNA_KC = 32                 # K22f: the row scale follows the running maximum over 32-column chunks
 PLANE_CHUNK = 128           # fsf_to_planes: one scale per (row, 128-channel chunk)
 K22F_ADDEND_CAP_EXP = 40    # K22f with a row addend: s_x * s_w <= 2^40
@@ -158,10 +159,11 @@ def dense_rows_classes(n):
 
 # ------------------------------------------------------------------------------------------------------------------ the formats
 def pick_scale(amax):
-    """The power of two s with s * amax in [2^13, 2^14) (s = 1 for amax = 0), float64, elementwise."""
+    """The power of two s with s * amax in [2^13, 2^14) (s = 1 for amax = 0; s = 2^126 for amax < 2^-113: the kernel's clamp), float64,
+    elementwise."""
     amax = np.asarray(amax, dtype=np.float64)
     _, ex = np.frexp(np.where(amax > 0, amax, 1.0))  # amax = f * 2^ex, f in [0.5, 1): floor(log2) = ex - 1
-    return np.where(amax > 0, np.exp2(TOP_EXP - (ex - 1).astype(np.float64)), 1.0)
+    return np.where(amax > 0, np.exp2(TOP_EXP - np.maximum(ex - 1, MIN_AMAX_EXP).astype(np.float64)), 1.0)
 
 
 def x_scales(x, rule, group=16):

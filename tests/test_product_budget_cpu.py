@@ -233,28 +233,48 @@ def _src(name):
 
 
 def test_scale_rules_and_caps_equal_the_kernel_sources():
-    planes, split, lna_h, lna, bwd = (_src(n) for n in ("spconv_planes.hip", "spconv_split.hip", "linear_norm_act.h", "linear_norm_act.hip",
-                                                         "spconv_bwd.hip"))
-    # the one scale rule: s * amax in [2^13, 2^14), s = 1 for amax = 0
-    for src, fn in ((planes, "sp_pick_scale"), (split, "scs_pick_scale"), (lna_h, "lna_pick_scale")):
-        body = src[src.index("void %s(float amax" % fn):][:500]
-        assert "e = amax > 0.0f ? (e < -113 ? -113 : e) : %d;" % P.TOP_EXP in body
-        assert "s = __uint_as_float((unsigned)(%d - e + 127) << 23);" % P.TOP_EXP in body
-    # the split and its floor: hi = rn_f16(x s), lo = rn_f16(x s - hi)
-    for src in (planes, lna_h):
-        assert "|x s - hi - lo| <= max(2^-22 |x s|, 2^-25)" in src
+    planes, split, lna_h, lna, bwd, fmt_h, fmt = (_src(n) for n in ("spconv_planes.hip", "spconv_split.hip", "linear_norm_act.h",
+                                                                     "linear_norm_act.hip", "spconv_bwd.hip", "operand_formats.h",
+                                                                     "operand_formats.hip"))
+    csrc_dir = os.path.join(ROOT, "fullysparsefusion_amd", "csrc")
+    others = {n: _src(n) for n in sorted(os.listdir(csrc_dir)) if n.endswith((".h", ".hip")) and n != "operand_formats.h"}
+    # the one scale rule: s * amax in [2^13, 2^14), s = 1 for amax = 0, the exponent clamped at -113 (s <= 2^126) — defined once
+    body = fmt_h[fmt_h.index("void fmt_pick_scale(float amax"):][:500]
+    assert "e = amax > 0.0f ? (e < -113 ? -113 : e) : %d;" % P.TOP_EXP in body
+    assert "s = __uint_as_float((unsigned)(%d - e + 127) << 23);" % P.TOP_EXP in body
+    assert len(re.findall(r"void \w*pick_scale\(", fmt_h)) == 1
+    # the split and its floor: hi = rn_f16(x s), lo = rn_f16(x s - hi) — defined once
+    assert "|x s - hi - lo| <= max(2^-22 |x s|, 2^-25)" in planes and "|x s - hi - lo| <= max(2^-22 |x s|, 2^-25)" in fmt_h
+    f16_body = fmt_h[fmt_h.index("void fmt_split_f16("):][:600]
+    for line in ("const float xs = __fmul_rn(v[e], s);", "h[e] = (_Float16)xs;", "l[e] = (_Float16)__fsub_rn(xs, (float)h[e]);"):
+        assert f16_body.count(line) == 1, line
+    assert fmt_h.count("__fsub_rn(xs, (float)h[e])") == 1
+    # no other file under csrc/ has a scale pick, a bf16 truncation split or an f16 split of its own
+    for name, src in others.items():
+        assert not re.search(r"void \w*pick_scale\(", src), name
+        assert "& 0xffff0000u" not in src and "__fsub_rn(xs, (float)h[e])" not in src, name
+        assert "%d - e + 127" % P.TOP_EXP not in src, name
     assert "(+ terms <= 3 * 2^-22 |x w|)" in planes and P.G_F16 == 3 * 2.0 ** -22
     # where the scales apply
     assert "const int nchunk = (c + %d) / %d;" % (P.PLANE_CHUNK - 1, P.PLANE_CHUNK) in planes        # fsf_to_planes: per (row, 128-channel chunk)
+    # ... over its team of 16 threads, in to_planes and in the pair sum
+    assert planes.count("for (int o = 8; o > 0; o >>= 1) amax = fmaxf(amax, __shfl_xor(amax, o, 16));\n    float s, inv;\n"
+                        "    fmt_pick_scale(amax, s, inv);") == 2
     assert "The weights get\n//     one power-of-two scale per layer" in planes                                   # K9c weights
     assert "one power-of-two scale per layer (s * max |w| in [2^13, 2^14))" in split                              # K9b-XP weights
-    assert "amax = fsf_wave_max(amax);\n    float s_row, inv_row;\n    lna_pick_scale(amax, s_row, inv_row);" in lna  # rows_to_planes: per row
-    # K22f / K22h weights: ONE max |w| word for the layer (every workgroup's atomicMax lands in hdr[2]), one lna_pick_scale of it
-    assert "atomicMax(hdr + 2, __float_as_uint(fmaxf(fmaxf(wave_max[0], wave_max[1]), fmaxf(wave_max[2], wave_max[3]))));" in lna
+    assert "amax = fsf_wave_max(amax);\n    float s_row, inv_row;\n    fmt_pick_scale(amax, s_row, inv_row);" in lna  # rows_to_planes: per row
+    # the f16 weights of every entry: ONE max |w| word for the layer (every workgroup's atomicMax lands in header word 2, one kernel,
+    # one host helper that all three prepare entries call), one fmt_pick_scale of it in the entry's prepare kernel
+    assert re.search(r"constexpr int FMT_HDR_AMAX_BITS = 2;", fmt_h) and re.search(r"constexpr int FMT_HDR_BYTES = 256;", fmt_h)
+    assert "atomicMax(hdr + FMT_HDR_AMAX_BITS, __float_as_uint(fmaxf(fmaxf(wave_max[0], wave_max[1]), fmaxf(wave_max[2], wave_max[3]))));" in fmt
+    assert sum(src.count("atomicMax(hdr + ") for src in others.values()) == 1
+    for src, kernel in ((lna, "lna_prepare_f16_kernel("), (split, "scs_prepare_f16_kernel("), (planes, "sp_weight_planes_kernel(")):
+        assert src.count("fsf_weight_layer_absmax(weight, ") == 1
+        prep = src[src.index(kernel):][:2000]
+        assert prep[:prep.index("\n}\n")].count("fmt_pick_scale(") == 1
+        assert "fmt_pick_scale(__uint_as_float(reinterpret_cast<const unsigned*>(hdr)[FMT_HDR_AMAX_BITS]), s" in prep
     prep = lna[lna.index("lna_prepare_f16_kernel("):][:2000]
-    assert prep.count("lna_pick_scale(") == 1
-    assert "lna_pick_scale(__uint_as_float(reinterpret_cast<const unsigned*>(hdr)[2]), s_w, inv_w);" in prep
-    assert prep.count("lna_split8_f16(v, s_w, hi, lo);") == 1
+    assert prep.count("fmt_split_f16(v, s_w, hi, lo);") == 1
     assert int(re.search(r"constexpr int LNA_KC = (\d+);", lna_h).group(1)) == P.LNA_KC
     assert "if (mb == 0u || s_new > xs_cur[rg]) { s_new = xs_cur[rg]; inv_new = xinv[rg]; }" in lna_h              # K22f: the scale only falls
     # the caps
@@ -269,7 +289,13 @@ def test_scale_rules_and_caps_equal_the_kernel_sources():
     term_a, term_b = (tuple(int(v) for v in re.search(r"constexpr int TERM_%s\[6\] = \{([0-9, ]+)\};" % ab, k10p).group(1).split(","))
                       for ab in "AB")
     assert sorted(zip(term_a, term_b)) == sorted(P.BF16_TERMS)
-    assert k10p.count("& 0xffff0000u") == 4 and "const float ar = __fsub_rn(a, ah), br = __fsub_rn(b, bh);" in k10p
+    # (the split is the shared one: two truncations per value, the remainders formed in fp32)
+    assert k10p.count("fmt_split_bf16(v, hi, mid, lo);") == 1
+    bf16_body = fmt_h[fmt_h.index("void fmt_split_bf16("):][:1400]
+    bf16_body = bf16_body[:bf16_body.index("\n}\n")]
+    assert bf16_body.count("& 0xffff0000u") == 4 and fmt_h.count("& 0xffff0000u") == 4
+    assert "const float ar = __fsub_rn(a, ah), br = __fsub_rn(b, bh);" in bf16_body and "const float al = __fsub_rn(ar, am), bl = __fsub_rn(br, bm);" in bf16_body
+    assert bf16_body.count("__builtin_amdgcn_perm(") == 3 and bf16_body.count("0x07060302u") == 3
     assert "  if (cap > 0 && ta == 128 && tb == 128) {\n" in bwd and bwd.count("spconv_bwd_weight_split_kernel, grid, dim3(256), BWS_SMEM") == 1
     assert (P.wgrad_kernel(64, 68), P.wgrad_kernel(68, 64), P.wgrad_kernel(68, 68), P.wgrad_kernel(P.WGRAD_CIN, P.WGRAD_COUT)) == ("K10", "K10", "K10p", "K10")
     # the pair range splits from 8 stages + 1 pair
@@ -282,6 +308,21 @@ def test_scale_rules_and_caps_equal_the_kernel_sources():
                  "const int64_t tiles = (int64_t)fsf_cdiv(cin, *ta) * fsf_cdiv(cout, *tb);"):
         assert line in bwd, line
     assert "cap = max(m_out, 1)" in open(os.path.join(ROOT, "fullysparsefusion_amd", "hip_ops.py")).read()  # rulebook_to_pairs
+
+
+def test_pick_scale_has_the_kernel_clamp():
+    """s * amax in [2^13, 2^14) down to amax = 2^-113; below it s stays 2^126 (fmt_pick_scale clamps the exponent so that s and 1 / s are
+    normal fp32 numbers), subnormal maxima included; s = 1 for amax = 0."""
+    amax = np.array([0.0, 2.0 ** -149, 2.0 ** -126, 2.0 ** -120, 1.5 * 2.0 ** -114, 2.0 ** -113, 1.99 * 2.0 ** -113, 2.0 ** -112, 1.0, 2.0 ** 13,
+                     1.5 * 2.0 ** 100, float(np.finfo(np.float32).max)])
+    s = P.pick_scale(amax)
+    assert s.tolist() == [1.0] + [2.0 ** 126] * 6 + [2.0 ** 125, 2.0 ** 13, 1.0, 2.0 ** -87, 2.0 ** -114]
+    assert P.MIN_AMAX_EXP == -113 and "(e < %d ? %d : e)" % (P.MIN_AMAX_EXP, P.MIN_AMAX_EXP) in _src("operand_formats.h")
+    s32 = s.astype(np.float32)
+    tiny = float(np.finfo(np.float32).tiny)
+    assert (s32 == s).all() and (s32 >= tiny).all() and ((1.0 / s).astype(np.float32) >= tiny).all()  # exact and normal, both ways
+    above = amax >= 2.0 ** -113
+    assert ((s * amax)[above] >= 2.0 ** 13).all() and ((s * amax)[above] < 2.0 ** 14).all()
 
 
 def test_weight_gradient_cases_on_both_sides_of_the_range_split():
