@@ -1907,8 +1907,8 @@ def test_nms_bev_binned_pairs_equal_all_pairs(ops, device, n):
 def test_linear_norm_act_segmax_equals_the_two_pass_form(ops, device, n, m, k, c, norm, act, grouped, long_seg):
     """K22s (`fsf_linear_norm_act_segmax`): rows sorted by segment -> the rows of fsf_linear_norm_act[_grouped] bit for bit, and the
     segment maxima of fsf_segment_reduce(mode max) over them bit for bit (max is exact, whatever the combination order: closed runs
-    inside a 16-row group, the LDS slots of a 128-row block, the carry across a workgroup's blocks, the atomic max across
-    workgroups); segment lengths from 1 to > 1e5 rows (a segment that spans many workgroups), one segment only, n = 1; output into a
+    inside a 16-row group, the LDS slots of a 128-row block, the atomic max for a segment that reaches beyond its block —
+    a carry from block to block of one workgroup was built, measured slower and dropped, see linear_norm_act.h); segment lengths from 1 to > 1e5 rows (a segment that spans many workgroups), one segment only, n = 1; output into a
     column slice of a wider buffer; `want_rows=False` writes no rows."""
     torch.manual_seed(n + m + k)
     if m == n:
